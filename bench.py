@@ -22,13 +22,23 @@ Workloads (``--workload``): ``config2`` (default; BASELINE config 2: 48 ch x 64^
 the metric is quoted on), ``real`` (the reference model's shapes [16 @ 80^3, 32 @ 40^3] -> 160^3,
 configs 4/5), ``c48l80`` (config 5's literal 48 ch x 80^3), ``config1`` (4 ch x 32^3).
 
-Prints ONE JSON line (rank 0): the contract keys plus "roofline" (dominant kernel: algorithmic bytes
-per launch / its average launch duration from HIP events on the launch stream inside the timed
-region), "rooflines" (the same for every stage), "step" (whole step against the bytes the pipeline
-really moves, SURVEY 8(d)'s compulsory floor and its stage-boundary model), "head_of_set",
-"real_shapes" (a short measurement of the N = 160 pipeline, default workload only) and
-"cpu_baseline" (the CPU oracle = restated reference path on this box's host cores, bounded sample,
-N = 1 only, with the parity of the GPU scores on the same rotations).
+Prints ONE JSON line (rank 0): the contract keys (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...) plus "roofline" (dominant kernel: algorithmic bytes per launch / its average launch
+duration from HIP events on the launch stream inside the timed region; HBM traffic from the committed
+profiles/ file), "rooflines" (the same for every stage) and "step" (whole step against the bytes the
+pipeline really moves, SURVEY 8(d)'s compulsory floor and its stage-boundary model).  A plain run does
+nothing else: set-up, warm-up, the timed steps, the outputs (``--dump-outputs``), the line.
+
+``--full`` adds every untimed extra: "head_of_set" and the top-K stage times, "sustained",
+"gather_check", "strong", "real_shapes" / "c48l80" / "real_protein" / "e3" (short measurements of
+other workloads, default workload only), "cpu_baseline" (the CPU oracle = restated reference path on
+this box's host cores, bounded sample, N = 1 only, with the parity of the GPU scores on the same
+rotations) and the roofline's traffic measured in the run (rocprofv3 --pmc child passes).
+
+``--dump-outputs DIR`` writes, after the timed steps, the ranked list they produced (what
+``DockingEngine.top_list`` hands a caller: rotation index, translation x / y / z, score) as
+DIR/top_rotation.npy, DIR/top_translation.npy (float64) and DIR/top_score.npy (float32).  The inputs
+are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -62,8 +72,13 @@ WORKLOADS = {   # name: (C fine, L, C coarse, rotation-set angle, description)
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (one launch of --batch rotations each)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every untimed extra (CPU baseline, counter passes, head of set, top-K stage times, sustained, "
+                         "gather_check, strong, other workloads); a plain run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write the ranked list of the timed steps as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=32, help="rotations per step = per launch (Docker.launch_batch: 32 since round 6, 16 before)")
     ap.add_argument("--workload", default="config2", choices=sorted(WORKLOADS))
     ap.add_argument("--channels", type=int, default=None, help="override the workload's channel count")
@@ -106,7 +121,10 @@ def parse_args():
                     help="kernel formulation of the channels-last K1 (include/dlpd.h, dlpd_zfft_channels_last_form): 0 = library default")
     ap.add_argument("--dry_run", action="store_true",
                     help="launch plumbing only (gloo, no GPU): every rank joins the group, rank 0 prints a JSON line")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -508,7 +526,7 @@ def run_rank(args):
     # CPU-baseline sample: cpu_rotations / 4 rotations from the head of each search group; their GPU scores
     # (each through the K1/K2 variant the search uses for it) are kept for the parity figure
     V_first = R_cpu = grp_cpu = None
-    if rank == 0 and world == 1 and args.cpu_rotations > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_rotations > 0:
         per = max(1, args.cpu_rotations // 4)
         sel, grp_cpu = [], []
         for k in range(4):
@@ -546,32 +564,36 @@ def run_rank(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, setup_s, host_inputs_s, device_setup_s = (float(v) for v in t.tolist())
     stages = timer.summary()                                 # K1/K2/K3 as measured inside the timed region
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, entries, N)
 
-    # untimed extras: (i) the head of the set (the z-dominant rotations, cheapest K1 gather); (ii) the top-K
+    # untimed extras (--full): (i) the head of the set (the z-dominant rotations, cheapest K1 gather); (ii) the top-K
     # kernels, which run on the side stream inside the timed region, serially on the main stream
-    time_steps(eng, Rd, idd, tr_of, qd_of, nb, h_first, 1)
-    eng.finish()
-    torch.cuda.synchronize()
-    ts = time.perf_counter()
-    time_steps(eng, Rd, idd, tr_of, qd_of, nb, h_first, head_n)
-    eng.finish()
-    torch.cuda.synchronize()
-    head_ms = (time.perf_counter() - ts) / head_n * 1e3
-    tk = StageTimer()
-    cs = eng.top.new_candidate_set() if eng.prefilter else None   # the steady-state path: candidate lists from K3
-    for i in range(h_first, h_first + min(3, head_n)):
-        sl = slice(i * nb, (i + 1) * nb)
-        V = eng.score_batch(Rd[sl], transposed=bool(tr_of[i * nb]), quads=bool(qd_of[i * nb]), cset=cs)
-        tk.mark("begin")
-        eng.select_batch(V, nb, eng._cset_used)
-        tk.mark("topk_select")
-        eng.merge_batch(idd[sl], nb)
-        tk.mark("topk_merge")
-    torch.cuda.synchronize()
-    stages.update(tk.summary())
+    head_ms = None
+    if args.full:
+        time_steps(eng, Rd, idd, tr_of, qd_of, nb, h_first, 1)
+        eng.finish()
+        torch.cuda.synchronize()
+        ts = time.perf_counter()
+        time_steps(eng, Rd, idd, tr_of, qd_of, nb, h_first, head_n)
+        eng.finish()
+        torch.cuda.synchronize()
+        head_ms = (time.perf_counter() - ts) / head_n * 1e3
+        tk = StageTimer()
+        cs = eng.top.new_candidate_set() if eng.prefilter else None   # the steady-state path: candidate lists from K3
+        for i in range(h_first, h_first + min(3, head_n)):
+            sl = slice(i * nb, (i + 1) * nb)
+            V = eng.score_batch(Rd[sl], transposed=bool(tr_of[i * nb]), quads=bool(qd_of[i * nb]), cset=cs)
+            tk.mark("begin")
+            eng.select_batch(V, nb, eng._cset_used)
+            tk.mark("topk_select")
+            eng.merge_batch(idd[sl], nb)
+            tk.mark("topk_merge")
+        torch.cuda.synchronize()
+        stages.update(tk.summary())
 
     sustained = None
-    if rank == 0 and world == 1 and args.sustained_s > 0:
+    if args.full and rank == 0 and world == 1 and args.sustained_s > 0:
         sustained = sustained_measurement(eng, R_all, seq_ids, seq_key, nb, N, elapsed / args.steps, args.sustained_s, dev)
 
     # untimed extras that EVERY world size runs, so that the driver's N = 1 and N = 8 lines can be compared:
@@ -582,8 +604,9 @@ def run_rank(args):
     switches = eng.switches()
     gather_check = strong = None
     all_ids = np.arange(nrot_total)
-    seq_all, _ = visiting_sequence(DockingEngine, R_all, all_ids, nb)
-    if args.gather_rotations > 0:
+    if args.full and (args.gather_rotations > 0 or args.strong_s > 0):
+        seq_all, _ = visiting_sequence(DockingEngine, R_all, all_ids, nb)
+    if args.full and args.gather_rotations > 0:
         sub = seq_all[:min(args.gather_rotations, len(seq_all))]
         ent, dt = sharded_search(eng, R_all, sub, rank, world, K, dist, dev)
         gather_check = {"rotations": int(len(sub)), "list_sha256": list_sha256(ent), "list_entries": int(len(ent[0])),
@@ -591,7 +614,7 @@ def run_rank(args):
                         "backend": (dist.get_backend() if dist is not None else None), "seconds": dt,
                         "sample": "the first %d rotations of the single-process visiting sequence, sharded r::W, one "
                                   "all-gather + deterministic merge; the hash is the same at every world size" % len(sub)}
-    if args.strong_s > 0:
+    if args.full and args.strong_s > 0:
         s_per_rot = elapsed / args.steps / nb
         complete = nrot_total / world * s_per_rot <= args.strong_s
         ids_strong = all_ids if complete else seq_all[:max(nb, int(args.strong_s / s_per_rot) // nb * nb)]
@@ -607,7 +630,7 @@ def run_rank(args):
                              "at this world size" % (len(ids_strong), args.strong_s))}
 
     real_shapes = c48l80 = e3 = real_protein = None
-    if rank == 0 and world == 1 and args.workload == "config2" and not args.no_real_shapes:
+    if args.full and rank == 0 and world == 1 and args.workload == "config2" and not args.no_real_shapes:
         del eng
         torch.cuda.empty_cache()
         real_shapes = short_measurement("real", args, dev, R_all, nb)
@@ -635,14 +658,14 @@ def run_rank(args):
         main_stages = [k for k in stages if k in alg and not k.startswith("topk")]
         dom = max(main_stages, key=lambda k: stages[k])
         traffic = traffic_src = None
-        if world == 1 and args.cpu_rotations > 0 and not args.no_pmc:
+        if args.full and world == 1 and args.cpu_rotations > 0 and not args.no_pmc:
             # the dominant kernel's HBM-side bytes measured NOW: two short child runs of this script under
             # rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE in separate passes, as the guide prescribes)
             traffic, traffic_src = live_pmc_traffic(args, dom, N, eng_hp)
         if traffic is None:
             traffic, traffic_src = pmc_traffic(args.workload, C, L, nb, dom)
         secondary = {}
-        if world == 1 and args.cpu_rotations > 0 and not args.no_pmc:
+        if args.full and world == 1 and args.cpu_rotations > 0 and not args.no_pmc:
             secondary = live_pmc_secondary(args, main_stages, N)
 
         def roof(k):
@@ -715,11 +738,12 @@ def run_rank(args):
             "stages": {k: {"ms_per_launch": v, "alg_GBps": (alg[k] / (v * 1e-3) / 1e9 if k in alg else None)}
                        for k, v in stages.items()},
             "step": step,
-            "head_of_set": {"value": nb * N ** 3 * world / (head_ms * 1e-3), "unit": "pose scores/s", "ms_per_step": head_ms,
-                            "sample": "the first %d batches of the visiting sequence (rotations about z, cheapest K1 gather); "
-                                      "untimed extra, NOT the headline" % head_n},
             "top_entries": int(len(entries[0])),
         }
+        if head_ms is not None:
+            out["head_of_set"] = {"value": nb * N ** 3 * world / (head_ms * 1e-3), "unit": "pose scores/s", "ms_per_step": head_ms,
+                                  "sample": "the first %d batches of the visiting sequence (rotations about z, cheapest K1 gather); "
+                                            "untimed extra, NOT the headline" % head_n}
         out["per_rank_setup_s"] = setup_s
         if dist is not None:       # rank 0's all-gather + merge: inside the timed region, and the untimed first one of the warm-up
             out["collective"] = {"gather_and_merge_s_in_timed_region": timed_gather_s, "first_gather_s_in_warmup": warm_gather_s}
@@ -750,6 +774,19 @@ def run_rank(args):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(dirname, entries, N):
+    """--dump-outputs: the ranked list of the timed steps as a caller of the search receives it (DockingEngine.top_list:
+    rotation index, translation x / y / z on the 2L grid, score), rotation and translation as float64 (exact)."""
+    import numpy as np
+    rot, idx, score, _ = entries
+    rot, idx = np.asarray(rot, dtype=np.int64), np.asarray(idx, dtype=np.int64)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "top_rotation.npy"), rot.astype(np.float64))
+    np.save(os.path.join(dirname, "top_translation.npy"),
+            np.stack([idx // (N * N), (idx // N) % N, idx % N], axis=1).astype(np.float64))
+    np.save(os.path.join(dirname, "top_score.npy"), np.asarray(score, dtype=np.float32))
 
 
 def sustained_measurement(eng, R_all, seq_ids, seq_key, nb, N, s_per_step, seconds, dev):

@@ -8,7 +8,7 @@ timeout 2400 python -m pytest tests -q -m gpu --durations=8 > $OUT/pytest_gpu.lo
 python -c "
 import __graft_entry__ as e
 e.build(); e.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 200 $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 200 $OUT/bench_default.err
 python -c "
 import json
 d = json.loads([l for l in open('$OUT/bench_default.json') if l.startswith('{')][0])

@@ -6,7 +6,7 @@ cd $ROOT
 OUT=gpurun_out/${1:-r06_d}
 mkdir -p $OUT
 timeout 1200 python -m pytest tests -m gpu -q -k "unwritten or dockE3 or tile_occupancy or maxpool or e3_plugin or occupancy_maps or replay or sweep" > $OUT/pytest.log 2>&1; tail -5 $OUT/pytest.log
-timeout 900 python bench.py --steps 40 --cpu_rotations 0 --sustained_s 0 --no_pmc > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --steps 40 --cpu_rotations 0 --sustained_s 0 --no_pmc > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

@@ -8,14 +8,14 @@ TAG=${1:-r06_z}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 timeout 2400 python -m pytest tests -q -m gpu --durations=12 -rx > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.err
-timeout 900 python bench.py --cpu_rotations 32 --no_real_shapes --sustained_s 0 --strong_s 0 --no_pmc > $OUT/bench_cpu32.json 2>/dev/null
-timeout 600 python bench.py --gpus 2 --backend gloo --same_device --cpu_rotations 0 --no_real_shapes --sustained_s 0 --strong_s 4 > $OUT/bench_two_ranks_one_gpu.json 2> $OUT/bench_two_ranks_one_gpu.err
-timeout 600 python bench.py --workload real --cpu_rotations 0 --no_pmc > $OUT/bench_real.json 2>/dev/null
-timeout 600 python bench.py --workload real_protein --cpu_rotations 0 --no_pmc > $OUT/bench_real_protein.json 2>/dev/null
-timeout 600 python bench.py --workload real_protein --k1_occupancy off --cpu_rotations 0 --no_pmc > $OUT/bench_real_protein_k1_occupancy_off.json 2>/dev/null
-timeout 600 python bench.py --workload c48l80 --cpu_rotations 0 --no_pmc > $OUT/bench_c48l80.json 2>/dev/null
-timeout 600 python bench.py --workload config1 --cpu_rotations 0 --no_pmc > $OUT/bench_config1.json 2>/dev/null
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.err
+timeout 900 python bench.py --full --cpu_rotations 32 --no_real_shapes --sustained_s 0 --strong_s 0 --no_pmc > $OUT/bench_cpu32.json 2>/dev/null
+timeout 600 python bench.py --full --gpus 2 --backend gloo --same_device --cpu_rotations 0 --no_real_shapes --sustained_s 0 --strong_s 4 > $OUT/bench_two_ranks_one_gpu.json 2> $OUT/bench_two_ranks_one_gpu.err
+timeout 600 python bench.py --full --workload real --cpu_rotations 0 --no_pmc > $OUT/bench_real.json 2>/dev/null
+timeout 600 python bench.py --full --workload real_protein --cpu_rotations 0 --no_pmc > $OUT/bench_real_protein.json 2>/dev/null
+timeout 600 python bench.py --full --workload real_protein --k1_occupancy off --cpu_rotations 0 --no_pmc > $OUT/bench_real_protein_k1_occupancy_off.json 2>/dev/null
+timeout 600 python bench.py --full --workload c48l80 --cpu_rotations 0 --no_pmc > $OUT/bench_c48l80.json 2>/dev/null
+timeout 600 python bench.py --full --workload config1 --cpu_rotations 0 --no_pmc > $OUT/bench_config1.json 2>/dev/null
 bash scripts/profile_gpu.sh ${TAG} > /dev/null 2>&1; cp gpurun_out/prof_${TAG}/summary.txt $OUT/summary.txt; cp gpurun_out/prof_${TAG}/kernel_stats.csv $OUT/kernel_stats.csv; cp gpurun_out/prof_${TAG}/command.txt $OUT/command.txt
 bash scripts/profile_gpu.sh ${TAG}_real --workload real > /dev/null 2>&1; cp gpurun_out/prof_${TAG}_real/summary.txt $OUT/real_shapes_summary.txt; cp gpurun_out/prof_${TAG}_real/kernel_stats.csv $OUT/real_shapes_kernel_stats.csv
 bash scripts/profile_gpu.sh ${TAG}_rp --workload real_protein > /dev/null 2>&1; cp gpurun_out/prof_${TAG}_rp/summary.txt $OUT/real_protein_summary.txt; cp gpurun_out/prof_${TAG}_rp/kernel_stats.csv $OUT/real_protein_kernel_stats.csv

@@ -861,7 +861,7 @@ def test_bench_multi_rank_leg_runs_the_hip_pipeline_with_two_ranks_on_this_gpu(d
     region ending in the all-gather + merge, the max-over-ranks reduction, `gather_check`, `strong` -- executed with the
     HIP kernels by TWO ranks on the one GPU of this box (gloo transport; RCCL wants one device per rank).  The merged
     list of the gather check must equal the single-process one (same sha256), and the line must carry the contract."""
-    common = ["--steps", "4", "--warmup", "2", "--cpu_rotations", "0", "--no_real_shapes", "--sustained_s", "0",
+    common = ["--full", "--steps", "4", "--warmup", "2", "--cpu_rotations", "0", "--no_real_shapes", "--sustained_s", "0",
               "--gather_rotations", "256"]
     two = _bench_line(["--gpus", "2", "--backend", "gloo", "--same_device", "--strong_s", "2"] + common)
     one = _bench_line(["--gpus", "1", "--strong_s", "0"] + common)
@@ -884,8 +884,8 @@ def test_bench_collectives_run_on_rccl_with_one_rank(dev):
     the process-group initialisation with `device_id`, the barriers, the all-gather of the device-resident list and the
     max-over-ranks reduction on a device tensor all run through RCCL itself; the merged list must equal the ungrouped
     run's (same sha256)."""
-    common = ["--gpus", "1", "--steps", "4", "--warmup", "2", "--cpu_rotations", "0", "--no_real_shapes", "--sustained_s", "0",
-              "--gather_rotations", "256", "--strong_s", "0"]
+    common = ["--full", "--gpus", "1", "--steps", "4", "--warmup", "2", "--cpu_rotations", "0", "--no_real_shapes", "--sustained_s",
+              "0", "--gather_rotations", "256", "--strong_s", "0"]
     rccl = _bench_line(["--force_group", "--backend", "nccl"] + common)
     plain = _bench_line(common)
     assert rccl["config"]["collective_backend"] == "nccl" and rccl["config"]["world_size_seen_by_the_collective"] == 1
@@ -893,6 +893,29 @@ def test_bench_collectives_run_on_rccl_with_one_rank(dev):
     assert rccl["gather_check"]["backend"] == "nccl" and rccl["gather_check"]["list_entries"] == 2000
     assert rccl["gather_check"]["list_sha256"] == plain["gather_check"]["list_sha256"]
     assert rccl["n_gpus"] == 1 and rccl["top_entries"] == 2000 and rccl["value"] > 0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_ranked_list(dev, tmp_path):
+    """A plain `bench.py` run: set-up, warm-up, the timed steps, the outputs, the line -- no untimed extra; its
+    --dump-outputs files are the ranked list of the timed steps, the same on a second run with the same arguments."""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--max_conf", "500"]
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        lines.append(_bench_line(common + ["--dump-outputs", d]))
+        dumps.append({n: np.load(os.path.join(d, "top_%s.npy" % n)) for n in ("rotation", "translation", "score")})
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "pose scores/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["value"] - line["config"]["rotations_per_step"] * 128 ** 3 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not set(line) & {"cpu_baseline", "sustained", "gather_check", "strong", "real_shapes", "e3", "head_of_set"}
+    out = dumps[0]
+    assert out["rotation"].dtype == np.float64 and out["translation"].dtype == np.float64 and out["score"].dtype == np.float32
+    assert out["rotation"].shape == (500,) and out["translation"].shape == (500, 3) and out["score"].shape == (500,)
+    assert np.all(np.diff(out["score"]) >= 0) and out["translation"].min() >= 0 and out["translation"].max() < 128
+    for n in out:
+        assert np.array_equal(out[n], dumps[1][n]), n
 
 
 def test_bench_refuses_same_device_with_rccl(dev):

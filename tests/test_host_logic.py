@@ -108,22 +108,47 @@ def test_rotations_generated_sets_match_soi_sizes():
     assert (torch.linalg.det(r.R[::997]) - 1).abs().max() < 1e-14
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/oim06.eul"), reason="reference data not present")
-def test_rotations_loader_reads_reference_files_incl_zero_padded_names(golden):
-    os.environ["DLPD_ROTATIONS_DIR"] = "/root/reference/data"
+def _write_soi_file(path, head, tail, n, seed):
+    """An SOI rotation file in the format the reference ships (``%f\\t %f\\t %f`` per line): ``head`` rows, then seeded
+    filler rows, then ``tail`` rows, ``n`` lines in all.  The SOI files themselves carry MitchellLab's licence and are not
+    redistributed; fixture G2 holds the first and last eight rows of each and what the reference's loader made of them.
+    -> the angles as written, parsed back from the text."""
+    rng = np.random.RandomState(seed)
+    mid = np.stack([rng.uniform(-np.pi, np.pi, n - 16), rng.uniform(0.0, np.pi, n - 16), rng.uniform(-np.pi, np.pi, n - 16)], 1)
+    text = "".join("%f\t %f\t %f\n" % tuple(a) for a in np.concatenate([head, mid, tail]))
+    with open(path, "w") as f:
+        f.write(text)
+    return np.array([[float(x) for x in line.split()] for line in text.splitlines()], dtype=np.float64)
+
+
+def test_rotations_loader_reads_reference_files_incl_zero_padded_names(golden, tmp_path):
+    from oracle import docking_oracle as orc
+    g = golden("g2_rotations.npz")
+    written = {}
+    for inc in (20, 15, 12, 10):
+        written[inc] = _write_soi_file(str(tmp_path / ("oim%02d.eul" % inc)), g["ang_first8_%d" % inc], g["ang_last8_%d" % inc],
+                                       int(g["n_%d" % inc]), inc)
+    for inc, n in ((6, 68760), (8, 29025)):       # the reference's loader asks for oim6.eul / oim8.eul and cannot open these
+        written[inc] = _write_soi_file(str(tmp_path / ("oim%02d.eul" % inc)), g["ang_first8_20"], g["ang_last8_20"], n, inc)
+    os.environ["DLPD_ROTATIONS_DIR"] = str(tmp_path)
     try:
-        g = golden("g2_rotations.npz")
         for inc in (20, 15, 12, 10):
             r = Rotations(inc, verbose=False)
+            assert r.source == str(tmp_path / ("oim%02d.eul" % inc))
             R = r.R.numpy()
             assert R.shape[0] == int(g["n_%d" % inc])
             np.testing.assert_allclose(R[:8], g["first8_%d" % inc], atol=1e-15)
             np.testing.assert_allclose(R[-8:], g["last8_%d" % inc], atol=1e-15)
-            np.testing.assert_allclose(R.sum(0), g["sum_%d" % inc], atol=1e-9)
+            # every row, in file order: against the oracle's conversion of the angles as written
+            ang = written[inc]
+            want = orc.euler_to_matrix(ang[:, 0], ang[:, 1], ang[:, 2])
+            np.testing.assert_allclose(R.sum(0), want.sum(0), atol=1e-9)
             w = np.arange(1, R.shape[0] + 1, dtype=np.float64)[:, None, None]
-            np.testing.assert_allclose((w * R).sum(0), g["wsum_%d" % inc], rtol=1e-12, atol=1e-6)
-        assert Rotations(6, verbose=False).R.shape[0] == 68760      # reference loader cannot open these
-        assert Rotations(8, verbose=False).R.shape[0] == 29025
+            np.testing.assert_allclose((w * R).sum(0), (w * want).sum(0), rtol=1e-12, atol=1e-6)
+        for inc, n in ((6, 68760), (8, 29025)):
+            r = Rotations(inc, verbose=False)
+            assert r.source == str(tmp_path / ("oim%02d.eul" % inc)) and r.R.shape[0] == n
+            np.testing.assert_allclose(r.R.numpy()[:8], g["first8_20"], atol=1e-15)
     finally:
         del os.environ["DLPD_ROTATIONS_DIR"]
 
@@ -239,6 +264,21 @@ def test_se3_scalar_representation_is_equivariant_and_shaped_like_the_reference(
     assert torch.allclose(k, k.flip(2)) and torch.allclose(k, k.transpose(2, 3))      # radial kernels
     # even box + stride 2 samples a rotated lattice, so only the full-resolution branch is exactly equivariant
     assert r1.shape == v1.shape
+
+
+def test_bench_dump_outputs_writes_the_ranked_list_as_the_caller_receives_it(tmp_path):
+    """bench.py --dump-outputs: the list of (rotation, flat index, score, pick) entries -> top_rotation / top_translation
+    (float64) and top_score (float32), entry for entry what DeviceTopList.to_top_list hands a caller."""
+    import bench
+    from deeplocalproteindocking_amd.engine import DeviceTopList
+    N = 128
+    rng = np.random.RandomState(0)
+    ent = (rng.randint(0, 68760, 50).astype(np.int64), rng.randint(0, N ** 3, 50).astype(np.int64),
+           np.sort(rng.randn(50).astype(np.float32)), rng.randint(0, 50, 50).astype(np.int64))
+    bench.dump_outputs(str(tmp_path / "out"), ent, N)
+    rot, tr, score = (np.load(str(tmp_path / "out" / ("top_%s.npy" % k))) for k in ("rotation", "translation", "score"))
+    assert rot.dtype == np.float64 and tr.dtype == np.float64 and score.dtype == np.float32
+    assert [(int(r), int(x), int(y), int(z), float(s)) for r, (x, y, z), s in zip(rot, tr, score)] == DeviceTopList.to_top_list(ent, N)
 
 
 def test_bench_reads_the_dominant_kernels_traffic_from_a_counter_pass(tmp_path, monkeypatch):
