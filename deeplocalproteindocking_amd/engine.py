@@ -114,6 +114,35 @@ class DeviceTopList:
         return [(int(rot[i]), int(x[i]), int(y[i]), int(z[i]), float(score[i])) for i in range(len(rot))]
 
 
+class _Grid:
+    """What one resolution grid of a search owns: the fine grid, or the coarse grid of the two-resolution model (half the
+    box, score channels only).  Sizes, pivot, crop and rotation scale; the ligand (and its channels-last or quad copy K1
+    gathers from), the receptor spectrum K2 reads, the K1 -> K2 workspaces; the state of the sparse K1 (set_ligand)."""
+
+    def __init__(self, eng, L, C, CT, center, extent, rot_scale, packed_receptor):
+        lib, dev, nb, f32 = eng.lib, eng.device, eng.batch, torch.float32
+        self.L, self.N, self.NZ, self.C, self.CT = L, 2 * L, L + 1, C, CT
+        self.center = float(L) / 2.0 if center is None else float(center)
+        self.extent, self.rot_scale = extent, float(rot_scale)
+        N, NZ = self.N, self.NZ
+        self.lig = torch.zeros(CT, L, L, L, dtype=f32, device=dev)
+        self.ligcl = torch.empty(lib.call("dlpd_channels_last_floats", C, L), dtype=f32, device=dev) if eng.use_cl else None
+        self.ligq = torch.empty(lib.call("dlpd_quads_floats", CT, L), dtype=f32, device=dev) if eng.use_quads else None
+        # boxes whose K2 re-reads the receptor spectrum for every rotation (80, 40) take a copy in the order its column
+        # phase consumes it (include/dlpd.h: dlpd_receptor_pack); written by set_receptor, read by untransposed launches
+        npk = lib.call("dlpd_receptor_packed_floats", CT, L) if packed_receptor else 0
+        self.recP = torch.zeros(npk, dtype=f32, device=dev) if npk else None
+        self.recF = None if (eng._spectrum_is_temporary and self.recP is not None) else \
+            torch.zeros(CT, NZ, N, N, 2, dtype=f32, device=dev)
+        self.wsA = torch.empty(nb * CT * NZ * L * L * 2, dtype=f32, device=dev)
+        self.wsB = torch.empty(nb * CT * NZ * N * N * 2, dtype=f32, device=dev)
+        # sparse K1: the ligand's cell map, the per-rotation maps, their pencil words (K2 goes by them where it reads
+        # the packed receptor), the decision and the fraction of cells occupied -- set by set_ligand
+        self.pencil_map_ok = self.recP is not None and bool(lib.call("dlpd_pencil_map_supported", L))
+        self.occ_src = self.occ_rot = self.pen = self.fill = None
+        self.sparse = self.pencil_map = False
+
+
 class DockingEngine:
     """Exhaustive translation scoring for batches of rotations of ONE receptor/ligand pair.
 
@@ -143,10 +172,8 @@ class DockingEngine:
         if not lib.call("dlpd_grid_supported", int(L)):
             raise RuntimeError("dlpd: box size L=%d has no compiled fused pipeline" % L)
         self.L, self.N, self.C = int(L), 2 * int(L), int(C)
-        self.NZ = self.N // 2 + 1
         self.has_clash = bool(has_clash)
         self.CT = self.C + (1 if self.has_clash else 0)
-        self.center = float(L) / 2.0 if center is None else float(center)
         # Conventions of the volume rotation and of VolumeConvolution(clip) that TorchProteinLibrary may define
         # differently (Utils/Conventions.py): scale + axis order are folded into the 3x3 maps K1 samples with.  The clash
         # channel follows where it comes from: re-projected ATOMS (clash_provider, the reference's own path,
@@ -154,10 +181,9 @@ class DockingEngine:
         # provider -- the synthetic configs) is a volume like the others and turns with the mapped matrix; clip_mode "input" clamps the receptor once
         # and every rotated ligand batch before its transform (through the volumes path: exact, one extra round trip of
         # the rotated volumes -- the price of a convention nobody has confirmed), "none" drops the clamp.
-        self.rot_scale = float(rotation_scale)
-        self.rot_scale1 = float(rotation_scale if coarse_rotation_scale is None else coarse_rotation_scale)
+        rot_scale1 = float(rotation_scale if coarse_rotation_scale is None else coarse_rotation_scale)
         self.rot_axis_order, self.rot_transpose = rotation_axis_order, bool(rotation_transpose)
-        self._rot_mapped = self.rot_scale != 1.0 or self.rot_scale1 != 1.0 or rotation_axis_order != "xyz" or self.rot_transpose
+        self._rot_mapped = float(rotation_scale) != 1.0 or rot_scale1 != 1.0 or rotation_axis_order != "xyz" or self.rot_transpose
         if clip_mode not in ("output", "input", "none"):
             raise RuntimeError("dlpd: clip_mode %r" % (clip_mode,))
         self.clip_mode = clip_mode
@@ -168,6 +194,8 @@ class DockingEngine:
         dev = self.device
         f32 = torch.float32
         self.C1 = int(coarse_channels)
+        # kernel formulation of the fused K3 (include/dlpd.h, dlpd_zifft_filter_form): 0 = the library's default
+        # (role-split transform / filter waves where compiled), 1 = channel-owning waves; same results bit for bit
         self.k3_form = int(k3_form)
         # kernel formulation of the channels-last K1 (include/dlpd.h, dlpd_zfft_channels_last_form): 0 = the library's
         # default, 1 = every wave gathers / transforms / stores in turn, 2 = role-split (boxes 64 and 80); same bits
@@ -179,18 +207,11 @@ class DockingEngine:
             # library refuses it at the first launch -- say so when the engine is built, not in the middle of a search
             raise RuntimeError("dlpd: k1_form=2 (role-split K1) exists in -DDLPD_TEST_VARIANTS builds only; this library "
                                "(%s) does not hold it" % getattr(lib, "path", "?"))
+        # fine_unfused (diagnostic / A-B): materialise the real correlations of the fine grid and run the
+        # vectorised filter kernel behind a plain z-inverse, instead of the fused z-inverse + MLP (K3)
         self.fine_unfused = bool(fine_unfused)
         self.set_filter(W1, b1, W2, b2)
-        nb, CT, NZ, N = self.batch, self.CT, self.NZ, self.N
-        self.lig = torch.zeros(CT, L, L, L, dtype=f32, device=dev)
-        self.recF = torch.zeros(CT, NZ, N, N, 2, dtype=f32, device=dev)
-        # boxes whose K2 re-reads the receptor spectrum for every rotation (80, 40) take a copy in the order its column
-        # phase consumes it (include/dlpd.h: dlpd_receptor_pack); written by set_receptor, read by untransposed launches
-        npk = lib.call("dlpd_receptor_packed_floats", CT, int(L)) if packed_receptor else 0
-        self.recP = torch.zeros(npk, dtype=f32, device=dev) if npk else None
-        self.recP1 = None
-        self.wsA = torch.empty(nb * CT * NZ * L * L * 2, dtype=f32, device=dev)
-        self.wsB = torch.empty(nb * CT * NZ * N * N * 2, dtype=f32, device=dev)
+        nb, CT, N = self.batch, self.CT, self.N
         self.V = torch.empty(nb, N, N, N, dtype=f32, device=dev)
         # channels-last gather (include/dlpd.h): one 16-byte load serves four channels of a corner, so the rotation
         # costs the same for every rotation; slab orientation and the quad layout are the per-channel kernel's
@@ -202,29 +223,21 @@ class DockingEngine:
             channels_last = self.C >= 8
         self.use_cl = bool(channels_last)
         self.extent = int(extent) if extent and int(extent) < int(L) else 0
-        self.extent1 = self.extent // 2
         if self.extent and self.clip_mode == "input":
             raise RuntimeError("dlpd: clip_mode 'input' is not combined with embedded boxes (use a compiled box size)")
         # (slab orientation needs K2's transposed reader: every compiled box except 80 in libdlpd.so)
         self.orient = bool(orient) and not self.use_cl and bool(lib.call("dlpd_orientation_supported", int(L)))
         self.use_quads = bool(quads) and not self.use_cl and not self.extent
-        if self.use_cl:
-            self.ligcl = torch.empty(lib.call("dlpd_channels_last_floats", self.C, int(L)), dtype=f32, device=dev)
         # With the channels-last K1 every launch is untransposed and goes through the staged path, so where K2 reads the
         # PACKED receptor copy (boxes 80 / 40) the natural-layout spectrum is dead once it has been packed: it becomes a
         # temporary of set_receptor instead of a second resident copy (282 MB at 17 channels, 813 MB at 49, box 80).
         self._spectrum_is_temporary = bool(self.use_cl and not keep_receptor_spectrum)
-        if self._spectrum_is_temporary and self.recP is not None:
-            self.recF = None
         self.prefilter = bool(prefilter)
         # Search-side sparsity (round 6): a ligand whose channels are zero in most 4^3 cells of its box (any real protein's
         # representation) gets per-rotation occupancy maps, and the channels-last K1 skips what they mark empty -- same
         # spectra.  None: decided per ligand and grid in set_ligand (on where the ligand's cells, dilated by one, stay below
         # SPARSE_K1_MAX_FILL of the box); True / False force it.
         self.sparse_k1_wanted = sparse_k1
-        self.sparse_k1 = self.sparse_k1_coarse = self.k2_pencil_map = self.k2_pencil_map_coarse = False
-        self._k2_by_map = {False: False, True: False}
-        self.lig_fill = self.lig_fill_coarse = None
         self.window = None
         if self.extent:
             # the reference's (2 extent)^3 translation grid inside this engine's (2L)^3 one: index t for 0 <= t <= extent
@@ -237,42 +250,24 @@ class DockingEngine:
             w, Nn = self.window, 2 * int(L)
             self.window_flat = ((w[:, None, None] * Nn + w[None, :, None]) * Nn + w[None, None, :]).reshape(-1).contiguous()
             self.prefilter = False
-        if self.use_quads:
-            self.ligq = torch.empty(lib.call("dlpd_quads_floats", CT, int(L)), dtype=f32, device=dev)
+        self.fine = _Grid(self, self.L, self.C, CT, center, self.extent, rotation_scale, packed_receptor)
+        self.coarse = None
         if self.C1:
             L1 = self.L // 2
             if self.L % 2 or not lib.call("dlpd_grid_supported", L1):
                 raise RuntimeError("dlpd: coarse box size %d has no compiled pipeline" % L1)
-            N1, NZ1, C1 = 2 * L1, L1 + 1, self.C1
-            self.L1 = L1
-            self.center1 = float(L1) / 2.0 if coarse_center is None else float(coarse_center)
-            self.lig1 = torch.zeros(C1, L1, L1, L1, dtype=f32, device=dev)
-            self.recF1 = torch.zeros(C1, NZ1, N1, N1, 2, dtype=f32, device=dev)
-            npk1 = lib.call("dlpd_receptor_packed_floats", C1, L1) if packed_receptor else 0
-            self.recP1 = torch.zeros(npk1, dtype=f32, device=dev) if npk1 else None
-            if self._spectrum_is_temporary and self.recP1 is not None:
-                self.recF1 = None
-            self.wsA1 = torch.empty(nb * C1 * NZ1 * L1 * L1 * 2, dtype=f32, device=dev)
-            self.wsB1 = torch.empty(nb * C1 * NZ1 * N1 * N1 * 2, dtype=f32, device=dev)
-            if self.use_quads:
-                self.ligq1 = torch.empty(lib.call("dlpd_quads_floats", C1, L1), dtype=f32, device=dev)
-            if self.use_cl:
-                self.ligcl1 = torch.empty(lib.call("dlpd_channels_last_floats", C1, L1), dtype=f32, device=dev)
-        # fine_unfused (diagnostic / A-B): materialise the real correlations of the fine grid and run the
-        # vectorised filter kernel behind a plain z-inverse, instead of the fused z-inverse + MLP (K3)
-        self.fine_unfused = bool(fine_unfused)
+            self.coarse = _Grid(self, L1, self.C1, self.C1, coarse_center, self.extent // 2, rot_scale1, packed_receptor)
+            # first-layer pre-activations of the coarse channels on the coarse grid (dlpd_zifft_preact): HP planes
+            self.pre = torch.empty(nb, self.HP, 2 * L1, 2 * L1, 2 * L1, dtype=f32, device=dev)
+        self.grids = [g for g in (self.fine, self.coarse) if g is not None]
         if self.fine_unfused:
             self.conv = torch.empty(nb, CT, N, N, N, dtype=f32, device=dev)
-        if self.C1:
-            # first-layer pre-activations of the coarse channels on the coarse grid (dlpd_zifft_preact): HP planes
-            self.pre = torch.empty(nb, self.HP, 2 * self.L1, 2 * self.L1, 2 * self.L1, dtype=f32, device=dev)
         self.top = DeviceTopList(self.K, nb, dev, lib)
         # optional: callable(R (nb,3,3) f32 device) -> (nb,L,L,L) f32 device ligand forbidden volumes
         # re-projected from rotated ATOMS (Docker.py:221-224) instead of the rotated volume
         self.clash_provider = None
-        # kernel formulation of the fused K3 (include/dlpd.h, dlpd_zifft_filter_form): 0 = the library's default
-        # (role-split transform / filter waves where compiled), 1 = channel-owning waves; same results bit for bit
-        self.k3_form = int(k3_form)
+        # step()'s double buffer, made at the first step (_start_steps); the batch whose select + merge is not issued yet
+        self._Vbuf = self._side = self._pending = None
 
     @property
     def _out_clip(self):
@@ -284,12 +279,12 @@ class DockingEngine:
     def _in_clip(self):
         return float(self.clip) if (self.clip is not None and self.clip_mode == "input") else None
 
-    def _kernel_R(self, R, coarse=False):
-        """The 3x3 maps K1 samples with: R itself, or scale * P R P (Utils/Conventions.kernel_matrices)."""
+    def _kernel_R(self, R, g):
+        """The 3x3 maps K1 samples with on grid g: R itself, or scale * P R P (Utils/Conventions.kernel_matrices)."""
         if not self._rot_mapped:
             return R
         from .Utils.Conventions import kernel_matrices
-        return kernel_matrices(R, self.rot_scale1 if coarse else self.rot_scale, self.rot_axis_order, self.rot_transpose)
+        return kernel_matrices(R, g.rot_scale, self.rot_axis_order, self.rot_transpose)
 
     def _k1_form_at(self, L):
         """The requested K1 formulation where the library holds both (boxes 64, 80); its only one elsewhere."""
@@ -297,17 +292,18 @@ class DockingEngine:
 
     def switches(self):
         """Which of the equivalent kernel formulations and which conventions this engine launches with (bench.py records it)."""
+        fine, c = self.fine, self.coarse
         return {"k1": "channels_last" if self.use_cl else "per_channel",
                 "k1_slab_orientation": bool(self.orient), "k1_quad_layout": bool(self.use_quads),
                 "k1_form": {0: "library default", 1: "phased", 2: "role-split"}[self.k1_form],
                 "k3_form": {0: "library default (role-split where compiled)", 1: "channel-owning", 2: "role-split"}[self.k3_form],
                 "k3_unfused": bool(self.fine_unfused), "topk_candidate_lists": bool(self.prefilter),
-                "k2_packed_receptor": {"fine": self.recP is not None, "coarse": self.recP1 is not None},
+                "k2_packed_receptor": {"fine": fine.recP is not None, "coarse": bool(c and c.recP is not None)},
                 "embedded_extent": self.extent or None,
-                "k1_occupancy_maps": {"fine": bool(self.sparse_k1), "coarse": bool(self.sparse_k1_coarse),
-                                      "k2_pencil_map": {"fine": bool(self.k2_pencil_map), "coarse": bool(self.k2_pencil_map_coarse)},
-                                      "ligand_cells_occupied": {"fine": self.lig_fill, "coarse": self.lig_fill_coarse}},
-                "rotation": {"center": self.center, "scale": self.rot_scale, "axis_order": self.rot_axis_order,
+                "k1_occupancy_maps": {"fine": fine.sparse, "coarse": bool(c and c.sparse),
+                                      "k2_pencil_map": {"fine": fine.pencil_map, "coarse": bool(c and c.pencil_map)},
+                                      "ligand_cells_occupied": {"fine": fine.fill, "coarse": c.fill if c else None}},
+                "rotation": {"center": fine.center, "scale": fine.rot_scale, "axis_order": self.rot_axis_order,
                              "transpose": self.rot_transpose},
                 "clip_mode": self.clip_mode}
 
@@ -321,7 +317,7 @@ class DockingEngine:
         HP = lib.call("dlpd_fused_hidden_pad", int(H), self.L, int(self.C1 > 0))
         if HP < 0:
             raise RuntimeError("dlpd: hidden width %d has no fused filter kernel at box %d" % (H, self.L))
-        if HP > 32 and (getattr(self, "fine_unfused", False) or self.k3_form == 1):
+        if HP > 32 and (self.fine_unfused or self.k3_form == 1):
             raise RuntimeError("dlpd: hidden width %d runs on the role-split K3 only" % H)
         if getattr(self, "HP", HP) != HP:
             raise RuntimeError("dlpd: a live engine keeps its hidden width (%d), got %d" % (self.HP, HP))
@@ -339,124 +335,67 @@ class DockingEngine:
         """rec_volumes (C,L,L,L); rec_forbidden (L,L,L); rec_coarse (C1,L/2,..).  Spectra precomputed
         once per pair (the reference recomputes them every batch inside VolumeConvolution,
         DockingModels.py:71)."""
-        L, N, CT = self.L, self.N, self.CT
-        if self.C1:
-            L1 = self.L1
-            r1 = torch.as_tensor(rec_coarse, dtype=torch.float32).reshape(self.C1, L1, L1, L1).to(self.device).contiguous()
-            if self._in_clip is not None:
-                r1 = r1.clamp(-self._in_clip, self._in_clip)
-            recF1 = self.recF1 if self.recF1 is not None else \
-                torch.empty(self.C1, L1 + 1, 2 * L1, 2 * L1, 2, dtype=torch.float32, device=self.device)
-            self.lib.call("dlpd_rfft3d_padded", _ptr(r1), _ptr(recF1), _ptr(self.wsA1), self.C1, L1,
-                          1.0 / float(2 * L1) ** 3, _stream(self.device))
-            if self.recP1 is not None:
-                self.lib.call("dlpd_receptor_pack", _ptr(recF1), _ptr(self.recP1), self.C1, L1, _stream(self.device))
-        rec = torch.zeros(CT, L, L, L, dtype=torch.float32, device=self.device)
-        rec[: self.C] = torch.as_tensor(rec_volumes, dtype=torch.float32).reshape(self.C, L, L, L).to(self.device)
-        if self._in_clip is not None:
-            rec[: self.C].clamp_(-self._in_clip, self._in_clip)
+        f32, dev, clip = torch.float32, self.device, self._in_clip
+        clamp = (lambda t: t) if clip is None else (lambda t: t.clamp(-clip, clip))
+        L, C = self.L, self.C
+        rec = torch.zeros(self.CT, L, L, L, dtype=f32, device=dev)
+        rec[:C] = clamp(torch.as_tensor(rec_volumes, dtype=f32).reshape(C, L, L, L).to(dev))
         if self.has_clash:
-            rec[self.C] = torch.as_tensor(rec_forbidden, dtype=torch.float32).reshape(L, L, L).to(self.device)
-        scale = 1.0 / float(N) ** 3
-        recF = self.recF if self.recF is not None else \
-            torch.empty(CT, self.NZ, N, N, 2, dtype=torch.float32, device=self.device)
-        self.lib.call("dlpd_rfft3d_padded", _ptr(rec), _ptr(recF), _ptr(self.wsA), CT, L, scale,
-                      _stream(self.device))
-        if self.recP is not None:
-            self.lib.call("dlpd_receptor_pack", _ptr(recF), _ptr(self.recP), CT, L, _stream(self.device))
-
-    def _k2(self, coarse, nb, tr, st):
-        """Stage K2 of the fine or the coarse grid on what K1 left in its wsA; tr: the slab orientation K1 used."""
-        wsA, rec, recP, wsB, CT, L = ((self.wsA1, self.recF1, self.recP1, self.wsB1, self.C1, self.L1) if coarse else
-                                      (self.wsA, self.recF, self.recP, self.wsB, self.CT, self.L))
-        by_map = self._k2_by_map[bool(coarse)]
-        if by_map is not False:
-            # K1 left the pencils of empty blocks unwritten: K2 takes them as zeros by the map (score channels only).  The map
-            # is the engine's own (rotation path: True) or the one made from the batch's volumes (a tensor)
-            assert recP is not None and not tr
-            self._k2_by_map[bool(coarse)] = False
-            pen = by_map if torch.is_tensor(by_map) else (self.pen_rot1 if coarse else self.pen_rot)
-            self.lib.call("dlpd_xy_correlate_packed_occ", _ptr(wsA), _ptr(recP), _ptr(wsB), nb, CT, L, _ptr(pen),
-                          self.C1 if coarse else self.C, st)
-        elif recP is not None and not tr:
-            self.lib.call("dlpd_xy_correlate_packed", _ptr(wsA), _ptr(recP), _ptr(wsB), nb, CT, L, st)
-        else:
-            if rec is None:          # (packed-receptor boxes drop the natural-layout spectrum: keep_receptor_spectrum=True keeps it)
-                raise RuntimeError("dlpd: this engine holds only the packed receptor spectrum; a transposed launch needs "
-                                   "keep_receptor_spectrum=True")
-            self.lib.call("dlpd_xy_correlate_oriented", _ptr(wsA), _ptr(rec), _ptr(wsB), nb, CT, L, 0, tr, st)
+            rec[C] = torch.as_tensor(rec_forbidden, dtype=f32).reshape(L, L, L).to(dev)
+        inputs = [(self.fine, rec)]
+        if self.coarse:
+            L1 = self.coarse.L
+            inputs.insert(0, (self.coarse, clamp(torch.as_tensor(rec_coarse, dtype=f32).reshape(self.C1, L1, L1, L1).to(dev)).contiguous()))
+        st = _stream(dev)
+        for g, r in inputs:
+            recF = g.recF if g.recF is not None else torch.empty(g.CT, g.NZ, g.N, g.N, 2, dtype=f32, device=dev)
+            self.lib.call("dlpd_rfft3d_padded", _ptr(r), _ptr(recF), _ptr(g.wsA), g.CT, g.L, 1.0 / float(g.N) ** 3, st)
+            if g.recP is not None:
+                self.lib.call("dlpd_receptor_pack", _ptr(recF), _ptr(g.recP), g.CT, g.L, st)
 
     SPARSE_K1_MAX_FILL = 0.7
 
     def _ligand_occupancy(self):
         """Cell maps of the stored ligand (all score channels) and the decision whether K1 goes by per-rotation maps."""
         from . import ops
-        self.sparse_k1 = self.sparse_k1_coarse = False
+        for g in self.grids:
+            g.sparse = g.pencil_map = False
         if not self.use_cl or self.sparse_k1_wanted is False:
             return
-        nc = (self.L + 3) // 4
 
         def reach(occ):
             """Fraction of the cells a ROTATED copy can mark: the per-rotation maps are conservative by about one cell per
             side, so the decision goes by the ligand's cells dilated by one (a 60 %-full coarse grid marks everything)."""
             o = occ.to(torch.float32).reshape(1, 1, *occ.shape[-3:])
             return float(torch.nn.functional.max_pool3d(o, kernel_size=3, stride=1, padding=1).mean())
-        self.occ_src = ops.tile_occupancy(self.lig[: self.C].unsqueeze(0), lib=self.lib)
-        self.lig_fill = float(self.occ_src.float().mean())
-        self.sparse_k1 = bool(self.sparse_k1_wanted) or reach(self.occ_src) < self.SPARSE_K1_MAX_FILL
-        if self.sparse_k1 and not hasattr(self, "occ_rot"):
-            self.occ_rot = torch.empty(self.batch, nc, nc, nc, dtype=torch.uint8, device=self.device)
-            self.pen_rot = torch.empty(self.batch, nc, dtype=torch.int32, device=self.device)
-        if self.C1:
-            nc1 = (self.L1 + 3) // 4
-            self.occ_src1 = ops.tile_occupancy(self.lig1.unsqueeze(0), lib=self.lib)
-            self.lig_fill_coarse = float(self.occ_src1.float().mean())
-            self.sparse_k1_coarse = bool(self.sparse_k1_wanted) or reach(self.occ_src1) < self.SPARSE_K1_MAX_FILL
-            if self.sparse_k1_coarse and not hasattr(self, "occ_rot1"):
-                self.occ_rot1 = torch.empty(self.batch, nc1, nc1, nc1, dtype=torch.uint8, device=self.device)
-                self.pen_rot1 = torch.empty(self.batch, nc1, dtype=torch.int32, device=self.device)
-        # Where K2 reads the packed receptor (boxes 80 / 40) it can go by a per-rotation PENCIL map: K1 then does not write
-        # the blocks without an occupied cell and K2 does not read the pencils the map marks empty (same spectra, same lists)
-        self.k2_pencil_map = bool(self.sparse_k1 and self.recP is not None and self.lib.call("dlpd_pencil_map_supported", self.L))
-        self.k2_pencil_map_coarse = bool(self.C1 and self.sparse_k1_coarse and self.recP1 is not None and
-                                         self.lib.call("dlpd_pencil_map_supported", self.L1))
-
-    def _k1_channels_last(self, coarse, R, nb, st):
-        """Rotation + z transform of the score channels from the channels-last copy, by occupancy maps where the ligand is sparse."""
-        call = self.lib.call
-        if coarse:
-            cl, wsA, C, CT, L, c0, ext, sparse = self.ligcl1, self.wsA1, self.C1, self.C1, self.L1, self.center1, self.extent1, self.sparse_k1_coarse
-            occ_src, occ_rot, pen, skip = (self.occ_src1, self.occ_rot1, self.pen_rot1, self.k2_pencil_map_coarse) if sparse else (None,) * 4
-        else:
-            cl, wsA, C, CT, L, c0, ext, sparse = self.ligcl, self.wsA, self.C, self.CT, self.L, self.center, self.extent, self.sparse_k1
-            occ_src, occ_rot, pen, skip = (self.occ_src, self.occ_rot, self.pen_rot, self.k2_pencil_map) if sparse else (None,) * 4
-        self._k2_by_map[bool(coarse)] = False
-        if sparse and self._k1_form_at(L) in (0, 1):
-            call("dlpd_rotated_occupancy", _ptr(occ_src), _ptr(R), _ptr(occ_rot), _ptr(pen) if skip else 0, nb, L, c0, st)
-            call("dlpd_zfft_channels_last_occ", _ptr(cl), _ptr(R), _ptr(occ_rot), _ptr(wsA), nb, C, CT, 0, L, c0, ext, int(skip), st)
-            self._k2_by_map[bool(coarse)] = bool(skip)        # this launch's K2 must go by the pencil map (wsA holds unwritten pencils)
-        else:
-            call("dlpd_zfft_channels_last_form", _ptr(cl), _ptr(R), _ptr(wsA), nb, C, CT, 0, L, c0, ext, self._k1_form_at(L), st)
+        for g in self.grids:
+            g.occ_src = ops.tile_occupancy(g.lig[: g.C].unsqueeze(0), lib=self.lib)
+            g.fill = float(g.occ_src.float().mean())
+            g.sparse = bool(self.sparse_k1_wanted) or reach(g.occ_src) < self.SPARSE_K1_MAX_FILL
+            if g.sparse and g.occ_rot is None:
+                nc = (g.L + 3) // 4
+                g.occ_rot = torch.empty(self.batch, nc, nc, nc, dtype=torch.uint8, device=self.device)
+                g.pen = torch.empty(self.batch, nc, dtype=torch.int32, device=self.device)
+            # Where K2 reads the packed receptor (boxes 80 / 40) it can go by a per-rotation PENCIL map: K1 then does not
+            # write the blocks without an occupied cell and K2 does not read the pencils the map marks empty (same spectra,
+            # same lists)
+            g.pencil_map = g.sparse and g.pencil_map_ok
 
     def set_ligand(self, lig_volumes, lig_forbidden=None, lig_coarse=None):
-        L = self.L
-        if self.C1:
-            self.lig1.copy_(torch.as_tensor(lig_coarse, dtype=torch.float32).reshape(self.lig1.shape))
-        self.lig[: self.C] = torch.as_tensor(lig_volumes, dtype=torch.float32).reshape(self.C, L, L, L).to(self.device)
+        L, fine, coarse = self.L, self.fine, self.coarse
+        if coarse:
+            coarse.lig.copy_(torch.as_tensor(lig_coarse, dtype=torch.float32).reshape(coarse.lig.shape))
+        fine.lig[: self.C] = torch.as_tensor(lig_volumes, dtype=torch.float32).reshape(self.C, L, L, L).to(self.device)
         if self.has_clash:
-            self.lig[self.C] = torch.as_tensor(lig_forbidden, dtype=torch.float32).reshape(L, L, L).to(self.device)
-        if self.use_cl:
-            st = _stream(self.device)
-            self.lib.call("dlpd_make_channels_last", _ptr(self.lig), _ptr(self.ligcl), self.C, L, st)
-            if self.C1:
-                self.lib.call("dlpd_make_channels_last", _ptr(self.lig1), _ptr(self.ligcl1), self.C1, self.L1, st)
+            fine.lig[self.C] = torch.as_tensor(lig_forbidden, dtype=torch.float32).reshape(L, L, L).to(self.device)
+        # the layout the rotation gather reads (include/dlpd.h), once per pair: channels-last, or quads (4x the ligand's bytes)
+        st = _stream(self.device)
+        for g in self.grids:
+            if self.use_cl:
+                self.lib.call("dlpd_make_channels_last", _ptr(g.lig), _ptr(g.ligcl), g.C, g.L, st)
+            elif self.use_quads:
+                self.lib.call("dlpd_make_quads", _ptr(g.lig), _ptr(g.ligq), g.CT, g.L, st)
         self._ligand_occupancy()
-        # quad layout for the rotation gather (include/dlpd.h), once per pair: 4x the ligand's bytes
-        if self.use_quads:
-            st = _stream(self.device)
-            self.lib.call("dlpd_make_quads", _ptr(self.lig), _ptr(self.ligq), self.CT, L, st)
-            if self.C1:
-                self.lib.call("dlpd_make_quads", _ptr(self.lig1), _ptr(self.ligq1), self.C1, self.L1, st)
 
     @staticmethod
     def prefers_quads(R):
@@ -476,6 +415,55 @@ class DockingEngine:
         return np.abs(R[:, 0, 2]) > np.abs(R[:, 1, 2])
 
     # ---- hot loop ------------------------------------------------------------------------
+    def _k1(self, g, R, nb, tr, quads, nch, st):
+        """K1 of grid g: rotation + z transform of its first nch ligand channels into channels [0, nch) of g.wsA, from the
+        channels-last copy (by occupancy maps where the ligand is sparse; score channels only), the quad layout or the
+        volume itself.  -> the pencil words K2 must go by (K1 left the pencils of empty blocks unwritten), or None."""
+        call, L, c0 = self.lib.call, g.L, g.center
+        if self.use_cl:
+            if g.sparse and self._k1_form_at(L) in (0, 1):
+                pen = g.pen if g.pencil_map else None
+                call("dlpd_rotated_occupancy", _ptr(g.occ_src), _ptr(R), _ptr(g.occ_rot), _ptr(pen), nb, L, c0, st)
+                call("dlpd_zfft_channels_last_occ", _ptr(g.ligcl), _ptr(R), _ptr(g.occ_rot), _ptr(g.wsA), nb, g.C, g.CT, 0, L,
+                     c0, g.extent, int(g.pencil_map), st)
+                return pen
+            call("dlpd_zfft_channels_last_form", _ptr(g.ligcl), _ptr(R), _ptr(g.wsA), nb, g.C, g.CT, 0, L, c0, g.extent,
+                 self._k1_form_at(L), st)
+        elif quads:
+            call("dlpd_zfft_quads", _ptr(g.ligq), _ptr(R), _ptr(g.wsA), nb, nch, g.CT, 0, L, c0, tr, st)
+        else:
+            call("dlpd_zfft_oriented_ext", _ptr(g.lig), _ptr(R), _ptr(g.wsA), nb, nch, g.CT, 0, L, 0, 1, c0, tr, g.extent, st)
+        return None
+
+    def _k1_volumes(self, g, vols, occ, st):
+        """K1 of grid g for given volumes (nb, C, L, L, L): z transform of the score channels, by their occupancy maps
+        if given.  -> the pencil words K2 must go by (where K2 reads the packed receptor, empty x-planes are not written
+        and K2 goes by the maps' OR over z), or None."""
+        call, nb, L = self.lib.call, vols.shape[0], g.L
+        if occ is None:
+            call("dlpd_zfft_into", _ptr(vols), 0, _ptr(g.wsA), nb, g.C, g.CT, 0, L, g.C * L ** 3, 0, 0.0, st)
+            return None
+        pen = None
+        if g.pencil_map_ok:
+            pen = torch.empty(nb, (L + 3) // 4, dtype=torch.int32, device=self.device)
+            call("dlpd_pencil_bits", _ptr(occ), _ptr(pen), nb, L, st)
+        call("dlpd_zfft_volumes_occ", _ptr(vols), _ptr(occ), _ptr(g.wsA), nb, g.C, g.CT, 0, L, g.C * L ** 3, int(pen is not None), st)
+        return pen
+
+    def _k2(self, g, nb, tr, pen, st):
+        """Stage K2 of grid g on what K1 left in its wsA; tr: the slab orientation K1 used; pen: the pencil words K1
+        returned (K2 takes the pencils they mark empty as zeros, score channels only)."""
+        if pen is not None:
+            assert g.recP is not None and not tr
+            self.lib.call("dlpd_xy_correlate_packed_occ", _ptr(g.wsA), _ptr(g.recP), _ptr(g.wsB), nb, g.CT, g.L, _ptr(pen), g.C, st)
+        elif g.recP is not None and not tr:
+            self.lib.call("dlpd_xy_correlate_packed", _ptr(g.wsA), _ptr(g.recP), _ptr(g.wsB), nb, g.CT, g.L, st)
+        else:
+            if g.recF is None:       # (packed-receptor boxes drop the natural-layout spectrum: keep_receptor_spectrum=True keeps it)
+                raise RuntimeError("dlpd: this engine holds only the packed receptor spectrum; a transposed launch needs "
+                                   "keep_receptor_spectrum=True")
+            self.lib.call("dlpd_xy_correlate_oriented", _ptr(g.wsA), _ptr(g.recF), _ptr(g.wsB), nb, g.CT, g.L, 0, tr, st)
+
     def score_batch(self, R, mark=None, out=None, volumes=None, transposed=False, quads=False, cset=None, occupancy=None):
         """R (nb,3,3) float32 on the device, nb <= batch.  Returns V[:nb] (view of the engine's
         buffer, overwritten by the next call): Docker.py:218-232.  mark(name): optional callback
@@ -493,74 +481,47 @@ class DockingEngine:
             return self._score_volumes(volumes, mark, out, cset, occupancy)
         nb = R.shape[0]
         assert nb <= self.batch and R.dtype == torch.float32 and R.is_contiguous()
-        tr = int(bool(transposed) and self.orient)
-        use_quads = bool(quads) and self.use_quads
-        has_clip, clip = self._out_clip
-        V = self.V if out is None else out
-        call, st, L = self.lib.call, _stream(self.device), self.L
         provider = self.clash_provider if self.has_clash else None
         if self._in_clip is not None:
             return self._score_rotated_then_clamped(R, mark, out, cset, provider)
-        R_true, R, R1 = R, self._kernel_R(R), (self._kernel_R(R, coarse=True) if self.C1 else None)
-        self._keepR = (R, R1)                          # mapped copies stay alive until the stream has consumed them
-        if not (self.C1 or provider or self.fine_unfused or mark or use_quads or self.use_cl or cset is not None or self.k3_form
-                or self.extent):
-            call("dlpd_score_rotations_oriented", _ptr(self.lig), _ptr(self.recF), _ptr(R), nb, self.C,
-                 int(self.has_clash), L, self.center, _ptr(self.W1t), _ptr(self.b1), _ptr(self.W2), self.b2,
-                 self.HP, has_clip, clip, self.threshold, _ptr(self.wsA), _ptr(self.wsB), _ptr(V), tr, st)
-            return V[:nb]
+        tr = int(bool(transposed) and self.orient)
+        use_quads = bool(quads) and self.use_quads
+        V = self.V if out is None else out
+        call, st, L = self.lib.call, _stream(self.device), self.L
+        fine, coarse = self.fine, self.coarse
+        Rk, Rk1 = self._kernel_R(R, fine), (self._kernel_R(R, coarse) if coarse else None)
+        self._keepR = (Rk, Rk1)                        # mapped copies stay alive until the stream has consumed them
         mark = mark or (lambda name: None)
         mark("begin")
-        if self.C1:
+        if coarse:
             # coarse resolution first: rotate + correlate + clip -> real volumes the fine filter reads
-            L1 = self.L1
-            if self.use_cl:
-                self._k1_channels_last(True, R1, nb, st)
-            elif use_quads:
-                call("dlpd_zfft_quads", _ptr(self.ligq1), _ptr(R1), _ptr(self.wsA1), nb, self.C1, self.C1, 0, L1,
-                     self.center1, tr, st)
-            else:
-                call("dlpd_zfft_oriented_ext", _ptr(self.lig1), _ptr(R1), _ptr(self.wsA1), nb, self.C1, self.C1, 0, L1, 0, 1,
-                     self.center1, tr, self.extent1, st)
+            pen = self._k1(coarse, Rk1, nb, tr, use_quads, coarse.C, st)
             sub = getattr(mark, "sub_stages", False)     # (diagnostic callers: a mark after every kernel of the coarse stage)
             if sub:
                 mark("coarse_k1")
-            self._k2(True, nb, tr, st)
+            self._k2(coarse, nb, tr, pen, st)
             if sub:
                 mark("coarse_k2")
-            self._coarse_preact(nb, has_clip, clip, st)
+            self._coarse_preact(nb, st)
             mark("coarse")
-        if provider is not None:
-            # clash channel from re-projected rotated ATOMS (Docker.py:221-224), scores from rotated volumes
-            forb = provider(R_true).reshape(nb, L, L, L).contiguous()
-            if self.use_cl:
-                self._k1_channels_last(False, R, nb, st)
-            elif use_quads:
-                call("dlpd_zfft_quads", _ptr(self.ligq), _ptr(R), _ptr(self.wsA), nb, self.C, self.CT, 0, L,
-                     self.center, tr, st)
-            else:
-                call("dlpd_zfft_oriented_ext", _ptr(self.lig), _ptr(R), _ptr(self.wsA), nb, self.C, self.CT, 0, L, 0, 1,
-                     self.center, tr, self.extent, st)
-            call("dlpd_zfft_oriented", _ptr(forb), 0, _ptr(self.wsA), nb, 1, self.CT, self.C, L, L ** 3, 0, 0.0,
-                 tr, st)                      # same orientation as the score channels
-        elif self.use_cl:
-            self._k1_channels_last(False, R, nb, st)
-            if self.has_clash:                # the ligand's forbidden volume: one channel, per-channel kernel
-                call("dlpd_zfft_oriented_ext", self.lig.data_ptr() + self.C * L ** 3 * 4, _ptr(R), _ptr(self.wsA), nb, 1,
-                     self.CT, self.C, L, 0, 1, self.center, 0, self.extent, st)
-        elif use_quads:
-            call("dlpd_zfft_quads", _ptr(self.ligq), _ptr(R), _ptr(self.wsA), nb, self.CT, self.CT, 0, L,
-                 self.center, tr, st)
-        else:
-            call("dlpd_zfft_oriented_ext", _ptr(self.lig), _ptr(R), _ptr(self.wsA), nb, self.CT, self.CT, 0, L, 0, 1,
-                 self.center, tr, self.extent, st)
+        # the clash channel goes in the score channels' launch where it is the stored forbidden volume and K1 per-channel;
+        # from re-projected rotated ATOMS (Docker.py:221-224) or beside the channels-last K1 it takes a launch of its own
+        forb = provider(R).reshape(nb, L, L, L).contiguous() if provider is not None else None
+        clash_apart = forb is not None or self.use_cl
+        pen = self._k1(fine, Rk, nb, tr, use_quads, fine.C if clash_apart else fine.CT, st)
+        if forb is not None:                  # same orientation as the score channels
+            call("dlpd_zfft_oriented", _ptr(forb), 0, _ptr(fine.wsA), nb, 1, fine.CT, fine.C, L, L ** 3, 0, 0.0, tr, st)
+        elif clash_apart and self.has_clash:  # the ligand's forbidden volume: one channel, per-channel kernel
+            call("dlpd_zfft_oriented_ext", fine.lig.data_ptr() + self.C * L ** 3 * 4, _ptr(Rk), _ptr(fine.wsA), nb, 1,
+                 fine.CT, fine.C, L, 0, 1, fine.center, 0, fine.extent, st)
         mark("k1_rotate_zfft")
-        return self._correlate_and_filter(nb, V, mark, tr, cset)
+        return self._correlate_and_filter(nb, V, mark, tr, cset, pen)
 
     def _score_volumes(self, volumes, mark, out, cset=None, occupancy=None):
         vl, vf, vc = volumes
         nb, L = vl.shape[0], self.L
         assert nb <= self.batch
+        fine, coarse = self.fine, self.coarse
         occ0, occ1 = occupancy if occupancy is not None else (None, None)
         if (occ0 is not None or occ1 is not None) and self._in_clip is not None:
             raise RuntimeError("dlpd: occupancy maps are not combined with clip_mode 'input' (the clamp reads every voxel)")
@@ -572,93 +533,72 @@ class DockingEngine:
             if o.dtype != torch.uint8 or o.device.type != self.device.type or o.numel() != n * nc ** 3:
                 raise RuntimeError("dlpd: occupancy map %s does not belong to %d volumes of box %d" % (tuple(o.shape), n, Lx))
             return o.contiguous()
-        occ0, occ1 = _occ(occ0, nb, L), (_occ(occ1, nb, self.L1) if self.C1 else None)
+        occ0, occ1 = _occ(occ0, nb, L), (_occ(occ1, nb, coarse.L) if coarse else None)
         f32c = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()
         call, st = self.lib.call, _stream(self.device)
-        has_clip, clip = self._out_clip
         V = self.V if out is None else out
         mark = mark or (lambda name: None)
         mark("begin")
         if self._in_clip is not None:                  # VolumeConvolution(clip) clamping its INPUTS (clip_mode "input")
             vl = f32c(vl).clamp(-self._in_clip, self._in_clip)
-            vc = f32c(vc).clamp(-self._in_clip, self._in_clip) if self.C1 else vc
-        if self.C1:
-            L1 = self.L1
+            vc = f32c(vc).clamp(-self._in_clip, self._in_clip) if coarse else vc
+        pen1 = None
+        if coarse:
+            L1 = coarse.L
             vc = f32c(vc).reshape(nb, self.C1, L1, L1, L1)
-            if occ1 is not None:
-                # (boxes whose K2 reads the packed receptor: empty x-planes are not written, K2 goes by the maps' OR over z)
-                skip1 = self.recP1 is not None and bool(self.lib.call("dlpd_pencil_map_supported", L1))
-                if skip1:
-                    self.pen_vol1 = torch.empty(nb, (L1 + 3) // 4, dtype=torch.int32, device=self.device)
-                    call("dlpd_pencil_bits", _ptr(occ1), _ptr(self.pen_vol1), nb, L1, st)
-                call("dlpd_zfft_volumes_occ", _ptr(vc), _ptr(occ1), _ptr(self.wsA1), nb, self.C1, self.C1, 0, L1, self.C1 * L1 ** 3,
-                     int(skip1), st)
-                self._k2_by_map[True] = self.pen_vol1 if skip1 else False
-            else:
-                call("dlpd_zfft", _ptr(vc), 0, _ptr(self.wsA1), nb, self.C1, L1, self.C1 * L1 ** 3, 0, 0.0, st)
-            self._k2(True, nb, 0, st)
-            self._coarse_preact(nb, has_clip, clip, st)
+            pen1 = self._k1_volumes(coarse, vc, occ1, st)
+            self._k2(coarse, nb, 0, pen1, st)
+            self._coarse_preact(nb, st)
             mark("coarse")
         vl = f32c(vl).reshape(nb, self.C, L, L, L)
-        if occ0 is not None:
-            skip0 = self.recP is not None and bool(self.lib.call("dlpd_pencil_map_supported", L))
-            if skip0:
-                self.pen_vol = torch.empty(nb, (L + 3) // 4, dtype=torch.int32, device=self.device)
-                call("dlpd_pencil_bits", _ptr(occ0), _ptr(self.pen_vol), nb, L, st)
-            call("dlpd_zfft_volumes_occ", _ptr(vl), _ptr(occ0), _ptr(self.wsA), nb, self.C, self.CT, 0, L, self.C * L ** 3, int(skip0), st)
-            self._k2_by_map[False] = self.pen_vol if skip0 else False
-        else:
-            call("dlpd_zfft_into", _ptr(vl), 0, _ptr(self.wsA), nb, self.C, self.CT, 0, L, self.C * L ** 3, 0, 0.0, st)
+        pen = self._k1_volumes(fine, vl, occ0, st)
         if self.has_clash:
             vf = f32c(vf).reshape(nb, L, L, L)
-            call("dlpd_zfft_into", _ptr(vf), 0, _ptr(self.wsA), nb, 1, self.CT, self.C, L, L ** 3, 0, 0.0, st)
+            call("dlpd_zfft_into", _ptr(vf), 0, _ptr(fine.wsA), nb, 1, fine.CT, fine.C, L, L ** 3, 0, 0.0, st)
         mark("k1_rotate_zfft")
-        self._keep = (vl, vf, vc, occ0, occ1)          # inputs stay alive until the stream has consumed them
-        return self._correlate_and_filter(nb, V, mark, 0, cset)
+        self._keep = (vl, vf, vc, occ0, occ1, pen, pen1)   # inputs and pencil words stay alive until the stream has consumed them
+        return self._correlate_and_filter(nb, V, mark, 0, cset, pen)
 
     def _score_rotated_then_clamped(self, R, mark, out, cset, provider):
         """clip_mode "input": the reference order is rotate (Docker.py:218) -> VolumeConvolution(clip) (DockingModels.py:71),
         so the clamp acts on the ROTATED ligand volumes: they are materialised by the stand-alone rotation kernel, clamped
         (in _score_volumes) and fed to the pipeline as given volumes.  The clash channel is never clamped (Docker.py:32,225:
         VolumeConvolution() without clip)."""
-        nb, L, call, st = R.shape[0], self.L, self.lib.call, _stream(self.device)
-        f32 = torch.float32
-        Rk, Rk1 = self._kernel_R(R), (self._kernel_R(R, coarse=True) if self.C1 else None)
+        nb, st, fine, coarse = R.shape[0], _stream(self.device), self.fine, self.coarse
+        Rk, Rk1 = self._kernel_R(R, fine), (self._kernel_R(R, coarse) if coarse else None)
         self._keepR = (Rk, Rk1)                        # alive until the stream has consumed them
-        vl = torch.empty(nb, self.C, L, L, L, dtype=f32, device=self.device)
-        call("dlpd_rotate_trilinear", _ptr(self.lig), _ptr(Rk), _ptr(vl), nb, self.C, L, 0, self.center, st)
+
+        def rotated(g, Rg, c0, nch):
+            v = torch.empty(nb, nch, g.L, g.L, g.L, dtype=torch.float32, device=self.device)
+            self.lib.call("dlpd_rotate_trilinear", g.lig.data_ptr() + c0 * g.L ** 3 * 4, _ptr(Rg), _ptr(v), nb, nch, g.L, 0,
+                          g.center, st)
+            return v
+        vl = rotated(fine, Rk, 0, self.C)
         vf = vc = None
         if self.has_clash:
-            if provider is not None:
-                vf = provider(R).reshape(nb, L, L, L).contiguous()
-            else:
-                vf = torch.empty(nb, 1, L, L, L, dtype=f32, device=self.device)
-                call("dlpd_rotate_trilinear", self.lig.data_ptr() + self.C * L ** 3 * 4, _ptr(Rk), _ptr(vf), nb, 1, L, 0,
-                     self.center, st)
-        if self.C1:
-            L1 = self.L1
-            vc = torch.empty(nb, self.C1, L1, L1, L1, dtype=f32, device=self.device)
-            call("dlpd_rotate_trilinear", _ptr(self.lig1), _ptr(Rk1), _ptr(vc), nb, self.C1, L1, 0,
-                 self.center1, st)
+            vf = provider(R).reshape(nb, self.L, self.L, self.L).contiguous() if provider is not None else rotated(fine, Rk, self.C, 1)
+        if coarse:
+            vc = rotated(coarse, Rk1, 0, self.C1)
         return self._score_volumes((vl, vf, vc), mark, out, cset)
 
-    def _coarse_preact(self, nb, has_clip, clip, st):
+    def _coarse_preact(self, nb, st):
         """Coarse grid, last stage: z-inverse + clip fused with the coarse half of the (linear) first layer
         (DockingModels.py:74-83): HP pre-activation planes on the coarse grid instead of C1 correlation volumes."""
-        self.lib.call("dlpd_zifft_preact_form", _ptr(self.wsB1), _ptr(self.pre), nb, self.C1, self.L1,
+        has_clip, clip = self._out_clip
+        self.lib.call("dlpd_zifft_preact_form", _ptr(self.coarse.wsB), _ptr(self.pre), nb, self.C1, self.coarse.L,
                       self.W1t.data_ptr() + self.C * self.HP * 4, _ptr(self.b1), self.HP, has_clip, clip, self.k3_form, st)
 
-    def _correlate_and_filter(self, nb, V, mark, tr, cset=None):
-        """K2 + K3 (+ filter) on whatever K1 left in wsA (and the coarse result in aux); tr: the slab
-        orientation K1 used."""
+    def _correlate_and_filter(self, nb, V, mark, tr, cset, pen):
+        """K2 + K3 (+ filter) on whatever K1 left in the fine wsA (and the coarse result in aux); tr: the slab
+        orientation K1 used; pen: the pencil words K1 returned."""
         has_clip, clip = self._out_clip
-        call, st, L = self.lib.call, _stream(self.device), self.L
-        self._k2(False, nb, tr, st)
+        call, st, L, fine = self.lib.call, _stream(self.device), self.L, self.fine
+        self._k2(fine, nb, tr, pen, st)
         mark("k2_xy_corr")
-        aux, C1, N1 = (_ptr(self.pre), self.C1, 2 * self.L1) if self.C1 else (0, 0, 0)
+        aux, C1, N1 = (_ptr(self.pre), self.C1, self.coarse.N) if self.coarse else (0, 0, 0)
         if self.fine_unfused:
             N3 = self.N ** 3
-            call("dlpd_zifft_real_part", _ptr(self.wsB), _ptr(self.conv), nb, self.CT, self.C, L, has_clip, clip, st)
+            call("dlpd_zifft_real_part", _ptr(fine.wsB), _ptr(self.conv), nb, self.CT, self.C, L, has_clip, clip, st)
             mark("k3_zifft")
             mask = self.conv.data_ptr() + self.C * N3 * 4 if self.has_clash else 0
             call("dlpd_filter_volumes", _ptr(self.conv), self.C, self.CT * N3, self.N, aux, C1, N1, int(C1 > 0), mask,
@@ -669,7 +609,7 @@ class DockingEngine:
             # fused K3; with a candidate set it also appends every score below the running K-th one to the batch's
             # candidate lists, which the top-K select then takes instead of a radix select over V
             tau, ck, cc, cap = (_ptr(self.top.tau), _ptr(cset["keys"]), _ptr(cset["count"]), cset["cap"]) if cset else (0, 0, 0, 0)
-            call("dlpd_zifft_filter_form", _ptr(self.wsB), _ptr(V), nb, self.C, int(self.has_clash), L,
+            call("dlpd_zifft_filter_form", _ptr(fine.wsB), _ptr(V), nb, self.C, int(self.has_clash), L,
                  _ptr(self.W1t), _ptr(self.b1), _ptr(self.W2), self.b2, self.HP, has_clip, clip, self.threshold,
                  aux, C1, int(C1 > 0), tau, ck, cc, cap, self.k3_form, st)
             self._cset_used = cset
@@ -697,26 +637,31 @@ class DockingEngine:
         self.top.merge(rot_ids, nb)
 
     # ---- two-stream pipeline: top-K of batch i overlaps K1/K2 of batch i+1 -----------------
+    def _start_steps(self):
+        """step()'s state, made at the first step: a V buffer and a candidate set per slot (two on the device, where
+        the side stream consumes one slot while the next batch fills the other; one with the emulated library, which
+        runs everything on one stream), the side stream, and per slot the event that frees it and the caller's rot_ids."""
+        cuda = self.device.type == "cuda"
+        self._Vbuf = [self.V, torch.empty_like(self.V)] if cuda else [self.V]
+        self._csets = [self.top.new_candidate_set() if self.prefilter else None for _ in self._Vbuf]
+        self._consumed = [None] * len(self._Vbuf)
+        self._ids_alive = [None] * len(self._Vbuf)
+        self._side = torch.cuda.Stream(device=self.device) if cuda else None
+        self._k = 0
+
     def step(self, R, rot_ids, mark=None, volumes=None, transposed=False, quads=False, occupancy=None):
         """One batch: score on the current stream; select + merge on a side stream (they are
         latency-bound one-block kernels that fit beside the FFT blocks).  V is double-buffered;
         call finish() before reading the list."""
         nb = R.shape[0] if volumes is None else volumes[0].shape[0]
-        if self.device.type != "cuda":                  # emulated library (tests): same calls, one stream
-            if self.prefilter and not hasattr(self, "_cset_cpu"):
-                self._cset_cpu = self.top.new_candidate_set()
+        if self._Vbuf is None:
+            self._start_steps()
+        if self._side is None:                          # emulated library (tests): same calls, one stream
             V = self.score_batch(R, mark=mark, volumes=volumes, transposed=transposed, quads=quads,
-                                 cset=getattr(self, "_cset_cpu", None), occupancy=occupancy)
+                                 cset=self._csets[0], occupancy=occupancy)
             self.select_batch(V, nb, self._cset_used)
             self.merge_batch(rot_ids, nb)
             return
-        if not hasattr(self, "_side"):
-            self._side = torch.cuda.Stream(device=self.device)
-            self._Vbuf = [self.V, torch.empty_like(self.V)]
-            self._csets = [self.top.new_candidate_set(), self.top.new_candidate_set()] if self.prefilter else [None, None]
-            self._consumed = [None, None]
-            self._ids_alive = [None, None]
-            self._k = 0
         k = self._k
         self._k ^= 1
         main = torch.cuda.current_stream(self.device)
@@ -739,7 +684,7 @@ class DockingEngine:
     def _launch_pending(self, main):
         """Enqueue select + merge of the batch that finished last on the side stream: after its scores are
         complete (ready) and after everything issued on the main stream so far."""
-        pend, self._pending = getattr(self, "_pending", None), None
+        pend, self._pending = self._pending, None
         if pend is None:
             return
         V, nb, rot_ids, ready, k, cset = pend
@@ -755,7 +700,7 @@ class DockingEngine:
         self._consumed[k] = done
 
     def finish(self):
-        if hasattr(self, "_side"):
+        if self._side is not None:
             main = torch.cuda.current_stream(self.device)
             self._launch_pending(main)
             main.wait_stream(self._side)

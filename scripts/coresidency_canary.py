@@ -60,7 +60,8 @@ def main(co_runner):
         eng = dk.engine
         # the kernels the 298 / 300 were measured with: the dense K1 / K2 (round 6's occupancy-map kernels, which this
         # protein-shaped ligand would take by default, have another footprint and rarely show it within 80 scorings)
-        eng.sparse_k1 = eng.sparse_k1_coarse = eng.k2_pencil_map = eng.k2_pencil_map_coarse = False
+        for g in eng.grids:
+            g.sparse = g.pencil_map = False
         R = torch.from_numpy(Rall[16:32]).to(device=dev, dtype=torch.float32).contiguous()
     else:
         torch.manual_seed(5)
@@ -74,8 +75,8 @@ def main(co_runner):
         eng.set_receptor(rec, recf, rec1)
         eng.set_ligand(lig, ligf, lig1)
         R = torch.from_numpy(_rots(16, seed=8)).float().to(dev).contiguous()
-    buffers = {"coarse_k1": lambda: eng.wsA1, "coarse_k2": lambda: eng.wsB1, "coarse": lambda: eng.pre, "k1_rotate_zfft": lambda: eng.wsA,
-               "k2_xy_corr": lambda: eng.wsB, "k3_zifft_filter": lambda: eng.V}
+    buffers = {"coarse_k1": lambda: eng.coarse.wsA, "coarse_k2": lambda: eng.coarse.wsB, "coarse": lambda: eng.pre,
+               "k1_rotate_zfft": lambda: eng.fine.wsA, "k2_xy_corr": lambda: eng.fine.wsB, "k3_zifft_filter": lambda: eng.V}
     ref = {}
 
     def record(name):

@@ -51,18 +51,17 @@ def one_search():
             if name == "coarse":
                 cur[name] = eng.pre.view(torch.int32).sum(dtype=torch.int64)
             elif name == "coarse_k1":
-                cur[name] = eng.wsA1.view(torch.int32).sum(dtype=torch.int64)
+                cur[name] = eng.coarse.wsA.view(torch.int32).sum(dtype=torch.int64)
                 if bb == 1:
-                    KEEP["wsA1"] = eng.wsA1.clone()
+                    KEEP["wsA1"] = eng.coarse.wsA.clone()
             elif name == "coarse_k2":
-                cur[name] = eng.wsB1.view(torch.int32).sum(dtype=torch.int64)
+                cur[name] = eng.coarse.wsB.view(torch.int32).sum(dtype=torch.int64)
             elif name == "k1_rotate_zfft":
-                cur[name] = eng.wsA.view(torch.int32).sum(dtype=torch.int64)
+                cur[name] = eng.fine.wsA.view(torch.int32).sum(dtype=torch.int64)
             elif name == "k2_xy_corr":
-                cur[name] = eng.wsB.view(torch.int32).sum(dtype=torch.int64)
+                cur[name] = eng.fine.wsB.view(torch.int32).sum(dtype=torch.int64)
             elif name == "k3_zifft_filter":
-                k = eng._k ^ 1 if hasattr(eng, "_k") else 0
-                cur[name] = eng._Vbuf[k].view(torch.int32).sum(dtype=torch.int64) if hasattr(eng, "_Vbuf") else eng.V.view(torch.int32).sum(dtype=torch.int64)
+                cur[name] = eng._Vbuf[eng._k ^ 1].view(torch.int32).sum(dtype=torch.int64)     # (step() has moved _k on already)
         mark.sub_stages = True
         eng.step(Rd[16 * b:16 * b + 16], ids[16 * b:16 * b + 16], mark=mark)
         sums.append(cur)
@@ -125,7 +124,7 @@ for rep in range(REPS):
         print("search %d: list identical %s; differing (batch, stage): %s" % (rep, lst == base_list, where[:8]), flush=True)
         if (1, "coarse_k1") in where and SHOWN[0] < 1:
             SHOWN[0] += 1
-            L1, C1 = eng.L1, eng.C1
+            L1, C1 = eng.coarse.L, eng.C1
             a = base_wsA1.view(16, C1, L1 + 1, L1, L1, 2)
             g = KEEP["wsA1"].view(16, C1, L1 + 1, L1, L1, 2)
             d = (a != g)

@@ -32,8 +32,8 @@ with torch.no_grad():
 torch.cuda.synchronize()
 eng = dk.engine
 Rb = torch.from_numpy(R[16:32]).to(device=dev, dtype=torch.float32).contiguous()
-BUF = {"coarse_k1": lambda: eng.wsA1, "coarse_k2": lambda: eng.wsB1, "coarse": lambda: eng.pre, "k1_rotate_zfft": lambda: eng.wsA,
-       "k2_xy_corr": lambda: eng.wsB, "k3_zifft_filter": lambda: eng.V}
+BUF = {"coarse_k1": lambda: eng.coarse.wsA, "coarse_k2": lambda: eng.coarse.wsB, "coarse": lambda: eng.pre,
+       "k1_rotate_zfft": lambda: eng.fine.wsA, "k2_xy_corr": lambda: eng.fine.wsB, "k3_zifft_filter": lambda: eng.V}
 ORDER = ("coarse_k1", "coarse_k2", "coarse", "k1_rotate_zfft", "k2_xy_corr", "k3_zifft_filter")
 ref = {}
 
@@ -128,7 +128,7 @@ for it in range(ITER):
             msg = "iteration %d: first differing stage %s, %d elements differ (flat indices %s ...), later stages %s" % (
                 it, first, n, idx[:6].tolist(), {k: diffs[k][0] for k in order[1:]})
             if first == "coarse_k1":
-                L1, C1 = eng.L1, eng.C1
+                L1, C1 = eng.coarse.L, eng.C1
                 dd = d.view(16, C1, L1 + 1, L1, L1, 2).nonzero()
                 a = ref[first].view(16, C1, L1 + 1, L1, L1, 2)
                 g = BUF[first]().view(16, C1, L1 + 1, L1, L1, 2)

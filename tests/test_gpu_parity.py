@@ -478,7 +478,7 @@ def test_k2_by_the_pencil_map_reads_no_unwritten_pencil(dev, L, C, lo, hi):
 
 
 @pytest.mark.gpu
-def test_search_of_a_protein_shaped_pair_is_the_same_with_and_without_occupancy_maps(dev):
+def test_search_of_a_protein_shaped_pair_is_the_same_with_and_without_occupancy_maps_on_both_grids(dev):
     """The reference's real shapes [16 @ 80^3, 32 @ 40^3] with blob-shaped ligand volumes: the engine picks K1 by occupancy
     maps + K2 by pencil maps on its own; the ranked list of 48 rotations equals the list of the dense kernels entry for
     entry, with the K1 -> K2 workspaces refilled with NaNs before every launch."""
@@ -507,8 +507,8 @@ def test_search_of_a_protein_shaped_pair_is_the_same_with_and_without_occupancy_
         for beg in range(0, 48, 16):
             if mode is None:
                 torch.cuda.synchronize()
-                eng.wsA.fill_(float("nan"))
-                eng.wsA1.fill_(float("nan"))
+                eng.fine.wsA.fill_(float("nan"))
+                eng.coarse.wsA.fill_(float("nan"))
             eng.step(Rd[beg:beg + 16], ids[beg:beg + 16])
         lists[mode] = eng.top_list()
         del eng

@@ -20,7 +20,7 @@ def _pair(L, C, seed=0):
     return rec, lig, recf, ligf, W1, b1, W2, b2
 
 
-def test_fused_pipeline_matches_oracle(emu):
+def test_fused_pipeline_and_fine_grid_spectrum_match_oracle(emu):
     L, C = 32, 4
     rec, lig, recf, ligf, W1, b1, W2, b2 = _pair(L, C)
     thr = 4000.0
@@ -29,7 +29,7 @@ def test_fused_pipeline_matches_oracle(emu):
     eng.set_receptor(rec, recf)
     eng.set_ligand(lig, ligf)
     ref = torch.fft.rfftn(torch.cat([rec, recf[None]]), s=(2 * L,) * 3, dim=(1, 2, 3)) / (2 * L) ** 3
-    mine = torch.view_as_complex(eng.recF).permute(0, 2, 3, 1)
+    mine = torch.view_as_complex(eng.fine.recF).permute(0, 2, 3, 1)
     assert (mine - ref).abs().max() < 1e-6 * ref.abs().max() + 1e-8
     V = eng.score_batch(torch.from_numpy(R).float().contiguous()).clone()
     for i in range(2):
@@ -998,7 +998,7 @@ def test_k1_by_occupancy_maps_gives_the_same_spectra_emulated(emu, L, C, lo, hi)
     _k1_occupancy_checks(emu, "cpu", L, C, 3, lo, hi)
 
 
-def test_engine_search_with_k1_occupancy_maps_gives_the_same_list_emulated(emu):
+def test_engine_search_with_k1_occupancy_maps_on_both_grids_gives_the_same_list_emulated(emu):
     """DockingEngine decides per ligand (cells occupied < SPARSE_K1_MAX_FILL): a blob-shaped two-resolution ligand is searched
     with the maps, a dense one without; switching the maps off gives the same list entry for entry."""
     from deeplocalproteindocking_amd.engine import DockingEngine
@@ -1028,7 +1028,8 @@ def test_engine_search_with_k1_occupancy_maps_gives_the_same_list_emulated(emu):
     eng2 = DockingEngine(L, C, W1, b1, W2, b2, max_conf=4, batch=2, device="cpu", lib=emu, coarse_channels=C1)
     eng2.set_receptor(rec, recf, rec1)
     eng2.set_ligand(rec, ligf, rec1)                                 # ... and on an undecided one: no maps
-    assert eng2.switches()["k1_occupancy_maps"]["fine"] is False and eng2.lig_fill == 1.0
+    sw = eng2.switches()["k1_occupancy_maps"]
+    assert sw["fine"] is False and sw["ligand_cells_occupied"]["fine"] == 1.0
 
 
 def _pencil_map_checks(lib, device, L, C, nb, lo, hi, seed=29):
@@ -1088,3 +1089,34 @@ def _pencil_map_checks(lib, device, L, C, nb, lo, hi, seed=29):
 @pytest.mark.parametrize("L,C,nb,lo,hi", [(40, 2, 2, (22, 3, 14), (31, 12, 26)), (80, 1, 1, (30, 41, 22), (44, 58, 35))])
 def test_k2_by_the_pencil_map_reads_no_unwritten_pencil_emulated(emu, L, C, nb, lo, hi):
     _pencil_map_checks(emu, "cpu", L, C, nb, lo, hi)
+
+
+def test_k2_goes_by_no_pencil_map_of_an_interrupted_batch_emulated(emu):
+    """K1 hands its pencil map to K2 as an argument: a batch interrupted between them (a ``mark`` that raises after a sparse
+    K1 left pencils unwritten) leaves nothing behind, and the next batch -- dense given volumes -- scores as on a fresh
+    engine (read by a stale pencil map, K2 would take its live pencils for zeros)."""
+    g = torch.Generator().manual_seed(31)
+    L, C, H = 40, 8, 4
+    lig = torch.zeros(C, L, L, L)
+    lig[:, 14:24, 14:24, 14:24] = torch.randn(C, 10, 10, 10, generator=g)
+    rec, recf, ligf = torch.randn(C, L, L, L, generator=g) * 0.1, torch.rand(L, L, L, generator=g), torch.rand(L, L, L, generator=g)
+    W1, b1 = torch.randn(H, C, generator=g), torch.randn(H, generator=g)
+    W2, b2 = torch.randn(1, H, generator=g), torch.randn(1, generator=g)
+    vols = (torch.randn(1, C, L, L, L, generator=g) * 0.1, torch.rand(1, L, L, L, generator=g), None)
+    R = torch.from_numpy(orc.euler_to_matrix([0.7], [1.2], [-0.4])).float().contiguous()
+
+    def engine():
+        eng = DockingEngine(L, C, W1, b1, W2, b2, threshold_clash=1e4, max_conf=4, batch=1, device="cpu", lib=emu, sparse_k1=True)
+        eng.set_receptor(rec, recf)
+        eng.set_ligand(lig, ligf)
+        assert eng.switches()["k1_occupancy_maps"]["k2_pencil_map"]["fine"] is True
+        return eng
+
+    def stop_after_k1(name):
+        if name == "k1_rotate_zfft":
+            raise RuntimeError("stopped after K1")
+    eng = engine()
+    with pytest.raises(RuntimeError, match="stopped after K1"):
+        eng.score_batch(R, mark=stop_after_k1)
+    V = eng.score_batch(None, volumes=vols).clone()
+    assert torch.equal(V, engine().score_batch(None, volumes=vols)) and float(V.abs().max()) > 0
