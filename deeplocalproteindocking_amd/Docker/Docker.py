@@ -121,6 +121,7 @@ def all_gather_top_entries(entries, K, world_size, process_group=None, device="c
     return DeviceTopList.merge_entries(parts, K)
 
 
+PROVIDER_BATCH_BYTES = 256 << 20      # score_poses: room for the per-pose clash volumes a clash_provider returns at a time
 LAUNCH_BATCH = 32      # rotations per launch of the fused pipeline (16 through round 5: EXPERIMENTS.md R6)
 
 
@@ -357,6 +358,172 @@ class Docker:
         if rows:
             self.log.write("\n".join(rows) + "\n")
         self.log.flush()
+
+    # ------------------------------------------------------------------ local docking: given poses (csrc/dlpd_local.h)
+    def score_poses(self, receptor_volumes, ligand_volumes, R, T, receptor_forbidden=None, ligand_forbidden=None,
+                    clash_provider=None, radius=0):
+        """Scores of GIVEN poses by direct correlation: (P, W, W, W) float32 on ``self.device``, W = 2 radius + 1; entry
+        [p, dx, dy, dz] is the pose (R[p], T[p] + (dx, dy, dz) - radius).  R (P, 3, 3) rotation matrices, T (P, 3) signed integer
+        translations in fine-grid voxels, |t| < box_size.  The GLOBAL search's conventions throughout -- this Docker's rotation
+        conventions, the model's clip and clash threshold, floor(t / 2) on the coarse grid -- so a pose of ``top_list`` gets the
+        score the search gave it: ``score_poses(rot.R[i], signed (x, y, z))[0, 0, 0, 0]``.  The volumes and the clash
+        arguments are ``dock_volumes``'s.  Poses are processed in batches sized from the kernel's workspace."""
+        model = self.docking_model
+        if receptor_forbidden is not None and ligand_forbidden is None and clash_provider is None:
+            raise Exception("score_poses: receptor_forbidden needs the ligand's side of the clash channel: ligand_forbidden or clash_provider")
+        # the model is scored in eval mode and handed back in the mode it came in (a scoring call inside a training loop)
+        was_training = bool(getattr(model, "training", False))
+        if was_training:
+            model.eval()
+        try:
+            return self._score_poses(receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius)
+        finally:
+            if was_training:
+                model.train()
+
+    def _score_poses(self, receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius):
+        from deeplocalproteindocking_amd import ops
+        model = self.docking_model
+        dev, lib = self.device, self._lib
+        rec = [torch.as_tensor(v, dtype=torch.float32) for v in receptor_volumes]
+        lig = [torch.as_tensor(v, dtype=torch.float32) for v in ligand_volumes]
+        rec = [v.reshape((-1,) + tuple(v.shape[-3:])).to(dev).contiguous() for v in rec]
+        lig = [v.reshape((-1,) + tuple(v.shape[-3:])).to(dev).contiguous() for v in lig]
+        L = rec[0].shape[-1]
+        if L != self.box_size:
+            raise Exception("Volume size does not match box_size", L, self.box_size)
+        scale = 1
+        if len(rec) == 2:
+            scale = L // rec[1].shape[-1]
+        if len(rec) > 2 or (len(rec) == 2 and (scale not in (1, 2) or rec[1].shape[-1] * scale != L)):
+            raise Exception("score_poses: one resolution, or two with the coarser at the same or half the edge")
+        cv = self.conventions
+        clip = getattr(model, "clip", 5.0) if cv.clip_mode != "none" else None
+        if clip is not None and cv.clip_mode == "input":
+            rec, lig = [v.clamp(-float(clip), float(clip)) for v in rec], [v.clamp(-float(clip), float(clip)) for v in lig]
+            clip = None
+        R = torch.as_tensor(np.asarray(R, dtype=np.float64) if not torch.is_tensor(R) else R).reshape(-1, 3, 3)
+        T = torch.as_tensor(np.asarray(T) if not torch.is_tensor(T) else T).reshape(-1, 3)
+        P, r = R.shape[0], int(radius)
+        if T.shape[0] != P:
+            raise Exception("score_poses: one translation per rotation", T.shape[0], P)
+        Td = T.to(torch.int32).to(dev).contiguous()
+        Rf = R.to(device=dev, dtype=torch.float32).contiguous()
+        has_clash = receptor_forbidden is not None
+        if has_clash:
+            rf = torch.as_tensor(receptor_forbidden, dtype=torch.float32).reshape(1, L, L, L).to(dev).contiguous()
+            lf = None
+            if clash_provider is None:
+                lf = torch.as_tensor(ligand_forbidden, dtype=torch.float32).reshape(1, L, L, L).to(dev).contiguous()
+        params = fused_filter_parameters(model)
+        W = 2 * r + 1
+        out = torch.empty(P, W, W, W, dtype=torch.float32, device=dev)
+        # batches: the provider's re-projected clash volumes are L^3 floats per pose
+        batch = max(1, min(P, PROVIDER_BATCH_BYTES // (4 * L ** 3))) if (has_clash and clash_provider is not None) else P
+        for beg in range(0, P, batch):
+            sl = slice(beg, min(P, beg + batch))
+            Rb, Tb = Rf[sl], Td[sl]
+            corr0 = ops.local_correlate(rec[0], lig[0], Tb, R=cv.matrices(Rb, L), radius=r, scale=1, coarse="floor",
+                                        center=self.rotation_pivot(L), lib=lib)
+            corr1 = None
+            if len(rec) == 2:
+                L1 = rec[1].shape[-1]
+                corr1 = ops.local_correlate(rec[1], lig[1], Tb, R=cv.matrices(Rb, L1), radius=ops.local_coarse_radius(r, scale), scale=scale,
+                                            coarse="floor", center=self.rotation_pivot(L1), lib=lib)
+            clash = None
+            if has_clash:
+                if clash_provider is not None:
+                    lfb = clash_provider(Rb).reshape(Rb.shape[0], 1, L, L, L).contiguous()
+                    clash = ops.local_correlate(rf, lfb, Tb, R=None, radius=r, lib=lib)
+                else:
+                    clash = ops.local_correlate(rf, lf, Tb, R=cv.matrices(Rb, L), radius=r, center=self.rotation_pivot(L), lib=lib)
+                clash = clash.reshape(Rb.shape[0], W, W, W)
+            res = None
+            if params is not None:
+                W1, b1, W2, b2 = params
+                res = ops.local_filter(corr0, corr1, clash, Tb, r, W1, b1, W2, b2, scale=scale, coarse="floor", clip=clip,
+                                       threshold=getattr(model, "threshold_clash", 0.0), lib=lib)
+            if res is not None:
+                out[sl] = res[0]
+            else:                                   # any other filter module is CALLED on the features
+                feat = ops.local_features(corr0, corr1, Tb, r, scale=scale, coarse="floor", clip=clip)
+                with torch.no_grad():
+                    V = model.filter(feat).reshape(Rb.shape[0], W, W, W).to(torch.float32)
+                if clash is not None:
+                    V = torch.lt(clash, model.threshold_clash).to(torch.float32) * V
+                out[sl] = V
+        return out
+
+    def signed_translation(self, x, y, z):
+        """Grid indices of the (2 box_size)^3 score volume -> signed shifts (Docker.py:115-120)."""
+        L, N = self.box_size, 2 * self.box_size
+        return tuple(int(v) - N if int(v) >= L else int(v) for v in (x, y, z))
+
+    def refine(self, receptor_volumes, ligand_volumes, receptor_forbidden=None, ligand_forbidden=None, clash_provider=None,
+               poses=None, perturbations=None, radius=1):
+        """Local refinement of a list of poses (default: ``self.top_list``, which is not touched): for pose
+        (i, x, y, z, score) and every Q of ``perturbations`` ((n, 3, 3); default ``local_perturbations(5, 1)``) the rotation
+        Q @ rot.R[i] is scored over the (2 radius + 1)^3 window round the pose's signed translation (``score_poses``) and the
+        best (Q, d) is kept -- the first Q and the lowest window index on a tie.  -> ``self.refined_list``: entries
+        (R float64 (3, 3), (tx, ty, tz) signed ints, score, position of the source pose in ``poses``), stable-sorted by score.
+        With the identity among the perturbations an entry is never worse than its re-scored source pose.
+        Every rank refines the whole (gathered) list; there is no collective here."""
+        from deeplocalproteindocking_amd.Utils.Rotations import local_perturbations
+        poses = list(self.top_list if poses is None else poses)
+        Q = local_perturbations(5.0, 1) if perturbations is None else perturbations
+        Q = torch.as_tensor(np.asarray(Q, dtype=np.float64) if not torch.is_tensor(Q) else Q).to(torch.float64).reshape(-1, 3, 3)
+        nq, npose, W = Q.shape[0], len(poses), 2 * int(radius) + 1
+        self.refined_list = []
+        if npose == 0:
+            return self.refined_list
+        base = torch.stack([self.rot.R[int(p[0])].to(torch.float64) for p in poses])           # (npose, 3, 3)
+        Rall = torch.matmul(Q[None], base[:, None])                                             # (npose, nq, 3, 3)
+        t = torch.tensor([self.signed_translation(p[1], p[2], p[3]) for p in poses], dtype=torch.int32)
+        Tall = t[:, None, :].expand(-1, nq, -1)
+        S = self.score_poses(receptor_volumes, ligand_volumes, Rall.reshape(-1, 3, 3), Tall.reshape(-1, 3), receptor_forbidden,
+                             ligand_forbidden, clash_provider, radius=radius)
+        S = S.reshape(npose, nq * W ** 3).cpu().numpy()
+        pick = np.argmin(S, axis=1)                          # first occurrence of the minimum: lowest (Q, d)
+        r = int(radius)
+        for n in range(npose):
+            q, d = divmod(int(pick[n]), W ** 3)
+            dx, dy, dz = d // (W * W) - r, (d // W) % W - r, d % W - r
+            tt = (int(t[n, 0]) + dx, int(t[n, 1]) + dy, int(t[n, 2]) + dz)
+            self.refined_list.append((Rall[n, q].numpy().copy(), tt, float(S[n, pick[n]]), n))
+        self.refined_list.sort(key=lambda e: e[2])
+        return self.refined_list
+
+    def write_refined_conformations(self):
+        """``self.refined_list`` in the format of ``write_conformations`` (13 tab-separated ``%f`` columns, the matrix taken
+        from the entry, ``randomize_rot`` undone the same way): Results.DockerParser reads it unchanged."""
+        if self.log is None:
+            return
+        undo = self.randR.squeeze().t().to(torch.double) if self.randomize_rot else None
+        rows = []
+        for R, tt, score, _ in getattr(self, "refined_list", []):
+            r = torch.as_tensor(R, dtype=torch.double)
+            t = torch.tensor(tt, dtype=torch.double) * self.resolution
+            if undo is not None:
+                t, r = undo @ t, undo @ r
+            cols = [float(v) for v in r.reshape(-1)] + [float(v) for v in t] + [score]
+            rows.append("\t".join("%f" % v for v in cols))
+        if rows:
+            self.log.write("\n".join(rows) + "\n")
+        self.log.flush()
+
+    def refine_prepared(self, prepared, perturbations=None, radius=1, poses=None):
+        """``refine`` for a target given as files: the ``PreparedPair`` the SE3 search ran on (``prepare`` / ``dockSE3``) holds
+        the volumes; the clash channel is re-projected from the rotated ligand atoms as ``dockSE3`` does (Docker.py:221-224)."""
+        if prepared.group != "SE3":
+            raise Exception("refine needs the ligand's volumes: SE3 pairs only", prepared.group)
+        be = self._need_backend()
+        L, res, dev = self.box_size, self.resolution, self.device
+        lc, ln, lo = prepared.ligand_atoms
+        with torch.no_grad():
+            def provider(Rb):
+                return be.project(lc, ln, lo, L, res, dev, R=Rb, shift=self.box_center, sum_types=True)
+            return self.refine(prepared.receptor_volumes, prepared.ligand_volumes, prepared.receptor_forbidden, None,
+                               clash_provider=provider, poses=poses, perturbations=perturbations, radius=radius)
 
     @property
     def rotation_center(self):

@@ -17,7 +17,7 @@ import os
 import torch
 from torch import nn
 
-from deeplocalproteindocking_amd.ops import VolumeConvolution, VolumeRotation, filter_volumes
+from deeplocalproteindocking_amd.ops import MultiplyVolumes, VolumeConvolution, VolumeRotation, filter_volumes, local_filter
 
 
 def init_weights(module):
@@ -118,3 +118,46 @@ class GlobalDockingModel(nn.Module):
         return self.filter(V).reshape(B, N, N, N)
 
     forward.dlpd_reference_forward = True      # what the fused kernels compute (fused_filter_parameters)
+
+
+class LocalDockingModel(nn.Module):
+    """Scores GIVEN poses -- one receptor / ligand pair, one translation, one number per batch entry: the reference's
+    ``LocalDockingModel`` (DockingModels.py:86-120; driven by LocalTrainer.score, LocalTrainer.py:146-177) with the same
+    surface: ``.representation``, ``.filter``, ``.mult``, ``save`` / ``load`` with the reference's file names,
+    ``forward(receptor, ligand, T)`` -> (B, 1).
+
+    INFERENCE ONLY: the correlation runs in a HIP kernel without a backward.  ``forward`` raises when autograd is enabled and a
+    parameter requires a gradient (call it under ``torch.no_grad()``), rather than return a tensor that silently has no graph.
+    A filter that is not the reference's MLP (or is wider than the kernel's hidden widths) is called on the (B, sum C) features."""
+    FILES = GlobalDockingModel.FILES
+
+    def __init__(self, representation, filter, lib=None):
+        super().__init__()
+        self.representation, self.filter = representation, filter
+        self.mult = MultiplyVolumes(lib=lib)
+        self._lib = lib
+
+    _paths = GlobalDockingModel._paths
+    save = GlobalDockingModel.save
+    load = GlobalDockingModel.load
+
+    def forward(self, receptor, ligand, T):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("dlpd: LocalDockingModel is inference only (no backward through the correlation kernel): "
+                               "call it under torch.no_grad()")
+        edge = float(receptor.shape[2])
+        # one correlation value per channel of every resolution: T lives on the input grid, each resolution reads it
+        # scaled to its own edge (MultiplyVolumes truncates the scaled value toward zero)
+        pairs = zip(self.representation(receptor), self.representation(ligand))
+        # (T * edge_i / edge in this order, in T's own precision: where the product is a whole number the truncation must see it)
+        features = torch.cat([self.mult(rv.contiguous(), lv.contiguous(), T * float(rv.shape[2]) / edge) for rv, lv in pairs],
+                             dim=1).contiguous()
+        params = mlp_parameters(self.filter)
+        if params is not None:
+            W1, b1, W2, b2 = params
+            B = features.shape[0]
+            zero_t = torch.zeros(B, 3, dtype=torch.int32, device=features.device)
+            out = local_filter(features.reshape(B, -1, 1, 1, 1), None, None, zero_t, 0, W1, b1, W2, b2, lib=self._lib)
+            if out is not None:
+                return out[0].reshape(B, 1)
+        return self.filter(features)

@@ -49,6 +49,26 @@ def euler_to_matrices(phi, theta, psi):
     return R
 
 
+def local_perturbations(angle_deg, steps=1):
+    """Small rotations round the identity for ``Docker.refine``: the rotation vectors (i, j, k) * angle_deg on the
+    (2 steps + 1)^3 lattice, as matrices (n, 3, 3) float64 (Rodrigues).  Deterministic; the identity comes first, the
+    others follow in lexicographic order of (i, j, k)."""
+    steps = int(steps)
+    rng = range(-steps, steps + 1)
+    vecs = [(0, 0, 0)] + [(i, j, k) for i in rng for j in rng for k in rng if (i, j, k) != (0, 0, 0)]
+    out = np.empty((len(vecs), 3, 3), dtype=np.float64)
+    for n, v in enumerate(vecs):
+        w = np.asarray(v, dtype=np.float64) * math.radians(float(angle_deg))
+        a = float(np.linalg.norm(w))
+        if a == 0.0:
+            out[n] = np.eye(3)
+            continue
+        k = w / a
+        K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        out[n] = np.eye(3) + math.sin(a) * K + (1.0 - math.cos(a)) * (K @ K)
+    return torch.from_numpy(out)
+
+
 def generated_set_size(angle_inc):
     nphi = int(round(360.0 / float(angle_inc)))
     nsphere = int(round(41252.96 / float(angle_inc) ** 2))

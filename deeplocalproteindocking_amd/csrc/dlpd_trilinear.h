@@ -1,0 +1,45 @@
+// The trilinear sample every rotation kernel of the library takes (dlpd_corr.hip: k_rotate, K1; dlpd_local.h: the local
+// correlation): ONE definition, so that a pose scored by direct correlation samples the ligand exactly as the search does.
+#pragma once
+#include <dlpd_platform.h>
+
+// ------------------------------------------------------------------------------------------
+// trilinear sample of a (L,L,L) volume at position (px,py,pz), zeros outside
+// ------------------------------------------------------------------------------------------
+DLPD_D float trilinear_fetch(const float* __restrict__ v, int L, float px, float py, float pz) {
+  // branch-free: out-of-box corners get weight 0 and a clamped (valid) address, so all loads are
+  // unconditional and in flight together; the two z-neighbours come from ONE 8-byte load
+  // (half the address-unit work of eight scalar gathers)
+  const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
+  const int ix = (int)fx, iy = (int)fy, iz = (int)fz;
+  const float ax = px - fx, ay = py - fy, az = pz - fz;
+  const int hi = L - 1;
+  const bool x0 = (ix >= 0) & (ix <= hi), x1 = (ix + 1 >= 0) & (ix + 1 <= hi);
+  const bool y0 = (iy >= 0) & (iy <= hi), y1 = (iy + 1 >= 0) & (iy + 1 <= hi);
+  const bool z0 = (iz >= 0) & (iz <= hi), z1 = (iz + 1 >= 0) & (iz + 1 <= hi);
+  const float wx0 = x0 ? 1.f - ax : 0.f, wx1 = x1 ? ax : 0.f;
+  const float wy0 = y0 ? 1.f - ay : 0.f, wy1 = y1 ? ay : 0.f;
+  const float wz0 = z0 ? 1.f - az : 0.f, wz1 = z1 ? az : 0.f;
+  const int cx0 = min(max(ix, 0), hi), cx1 = min(max(ix + 1, 0), hi);
+  const int cy0 = min(max(iy, 0), hi), cy1 = min(max(iy + 1, 0), hi);
+  const int zb = min(max(iz, 0), hi - 1);          // pair (zb, zb+1) always inside the row
+  const int d = iz - zb;                           // 0 inside; -1 / +1 at the two faces
+  DLPD_PAIR p00 = dlpd_load_pair(v + (cx0 * L + cy0) * L + zb);
+  DLPD_PAIR p01 = dlpd_load_pair(v + (cx0 * L + cy1) * L + zb);
+  DLPD_PAIR p10 = dlpd_load_pair(v + (cx1 * L + cy0) * L + zb);
+  DLPD_PAIR p11 = dlpd_load_pair(v + (cx1 * L + cy1) * L + zb);
+  // value at z0 = iz is .x unless iz = zb+1 ; value at z1 = iz+1 is .y unless iz+1 = zb
+  const float v000 = d > 0 ? p00.y : p00.x, v001 = d < 0 ? p00.x : p00.y;
+  const float v010 = d > 0 ? p01.y : p01.x, v011 = d < 0 ? p01.x : p01.y;
+  const float v100 = d > 0 ? p10.y : p10.x, v101 = d < 0 ? p10.x : p10.y;
+  const float v110 = d > 0 ? p11.y : p11.x, v111 = d < 0 ? p11.x : p11.y;
+  float acc = v000 * (wx0 * wy0 * wz0);
+  acc += v001 * (wx0 * wy0 * wz1);
+  acc += v010 * (wx0 * wy1 * wz0);
+  acc += v011 * (wx0 * wy1 * wz1);
+  acc += v100 * (wx1 * wy0 * wz0);
+  acc += v101 * (wx1 * wy0 * wz1);
+  acc += v110 * (wx1 * wy1 * wz0);
+  acc += v111 * (wx1 * wy1 * wz1);
+  return acc;
+}

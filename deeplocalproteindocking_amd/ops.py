@@ -277,3 +277,140 @@ def maxpool3d_5s2(x, lib=None, occupancy=None, return_occupancy=False, unwritten
     lib.call("dlpd_maxpool3d_5s2_sparse", _ptr(x), _ptr(y), _ptr(occupancy.contiguous()) if occupancy is not None else None,
              _ptr(occ_out), B, C, D, int(bool(unwritten)), _stream(x.device))
     return (y, occ_out) if return_occupancy else y
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Local docking: direct correlation at given poses (csrc/dlpd_local.h)
+# ------------------------------------------------------------------------------------------------------------------
+COARSE_MODES = {"floor": 0, "trunc": 1}
+LOCAL_WS_BYTES = 256 << 20          # cap of the partial-sum workspace: poses are processed in batches that fit it
+
+
+def _pose_volumes(v, P, name, lib):
+    """(C, L, L, L) shared by all poses -> stride 0; (P, C, L, L, L) -> one set per pose."""
+    v = _check(v, name, lib)
+    if v.dim() == 4:
+        return v, 0
+    if v.dim() != 5 or v.shape[0] != P:
+        raise RuntimeError("dlpd: %s must be (C, L, L, L) or (P, C, L, L, L) with P = %d, got %s" % (name, P, tuple(v.shape)))
+    return v, v.shape[1] * v.shape[2] ** 3
+
+
+def local_correlate(receptor, ligand, T, R=None, radius=0, scale=1, coarse="floor", center=None, lib=None):
+    """corr (P, C, W, W, W), W = 2 radius + 1: corr[p, c, d] = sum_x receptor[c, x + coarse(T_p) + d] * ligand'[c, x], ligand' the
+    ligand rotated by R_p (the 3x3 maps ``VolumeRotation`` samples with; None: as it is) -- the slices of
+    MultiplyVolumes.multiply (MultiplyVolumes.py:13-47) summed directly.  receptor / ligand: (C, L, L, L) for all poses or
+    (P, C, L, L, L); T (P, 3) int32 signed translations on the grid of ``scale`` * L points; coarse(t) = floor(t / scale)
+    ("floor": the global search's index) or trunc(t / scale) ("trunc": Python's int())."""
+    lib_ = lib or get_lib()
+    T = T.contiguous()
+    if T.dtype != torch.int32 or T.dim() != 2 or T.shape[1] != 3:
+        raise RuntimeError("dlpd: T must be a (P, 3) int32 tensor")
+    P = T.shape[0]
+    rec, rs = _pose_volumes(receptor, P, "receptor", lib)
+    lig, ls = _pose_volumes(ligand, P, "ligand", lib)
+    C, L = rec.shape[-4], rec.shape[-1]
+    if tuple(lig.shape[-4:]) != tuple(rec.shape[-4:]):
+        raise RuntimeError("dlpd: local_correlate shape mismatch %s vs %s" % (tuple(rec.shape), tuple(lig.shape)))
+    if R is not None:
+        R = _check(R, "R", lib)
+        if R.shape[0] != P:
+            raise RuntimeError("dlpd: local_correlate needs one matrix per pose")
+    r, W = int(radius), 2 * int(radius) + 1
+    per = lib_.call("dlpd_local_ws_bytes", 1, C, L, r)
+    if per == 0:
+        raise RuntimeError("dlpd: local_correlate supports boxes 2..128 and radius 0..3 (box %d, radius %d)" % (L, r))
+    dev = rec.device
+    if T.device != dev or lig.device != dev or (R is not None and R.device != dev):
+        raise RuntimeError("dlpd: local_correlate arguments must be on one device")
+    out = torch.empty(P, C, W, W, W, dtype=torch.float32, device=dev)
+    chunk = max(1, min(P, LOCAL_WS_BYTES // per, lib_.call("dlpd_local_max_poses", C, L)))      # workspace and launch-grid limits
+    ws = torch.empty(per * chunk, dtype=torch.uint8, device=dev)
+    c0 = float(L) / 2.0 if center is None else float(center)
+    st = _stream(dev)
+    for beg in range(0, P, chunk):
+        n = min(chunk, P - beg)
+        lib_.call("dlpd_local_correlate", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg,
+                  (_ptr(R) + 36 * beg) if R is not None else None, _ptr(T) + 12 * beg, _ptr(out) + 4 * C * W ** 3 * beg, _ptr(ws),
+                  n, C, L, r, int(scale), COARSE_MODES[coarse], c0, rs, ls, st)
+    return out
+
+
+def local_coarse_radius(radius, scale):
+    """Window radius on the coarser grid that covers coarse(t + d) for every |d| <= radius (either convention)."""
+    return int(radius) if int(scale) == 1 else (int(radius) + 1) // 2
+
+
+def local_features(corr0, corr1, T, radius, scale=1, coarse="floor", clip=None):
+    """The filter's input rows (P * W^3, C0 + C1) from the window correlations, in torch: for a filter module that has to be
+    CALLED (not the reference MLP, or wider than the kernel's hidden widths)."""
+    P, C0, W = corr0.shape[0], corr0.shape[1], corr0.shape[2]
+    feats = [corr0.reshape(P, C0, -1)]
+    if corr1 is not None:
+        r, rc = int(radius), local_coarse_radius(radius, scale)
+        d = torch.arange(-r, r + 1, device=corr0.device)
+        t = T.to(torch.int64)
+
+        def co(v):
+            return torch.div(v, int(scale), rounding_mode="floor" if coarse == "floor" else "trunc")
+        k = co(t[:, :, None] + d[None, None, :]) - co(t)[:, :, None] + rc               # (P, 3, W)
+        Wc = 2 * rc + 1
+        flat = ((k[:, 0, :, None, None] * Wc + k[:, 1, None, :, None]) * Wc + k[:, 2, None, None, :]).reshape(P, 1, -1)
+        c1 = corr1.reshape(P, corr1.shape[1], -1)
+        feats.append(torch.gather(c1, 2, flat.expand(-1, c1.shape[1], -1)))
+    f = torch.cat(feats, dim=1)
+    if clip is not None:
+        f = f.clamp(-float(clip), float(clip))
+    return f.permute(0, 2, 1).reshape(P * W ** 3, -1)
+
+
+def local_filter(corr0, corr1, clash, T, radius, W1, b1, W2, b2, scale=1, coarse="floor", clip=None, threshold=0.0, lib=None):
+    """score (P, W, W, W), best score (P), best flat window index (P) int32 from the window correlations of
+    ``local_correlate``: clamp, coarse index, SimpleFilter MLP (DockingModels.py:28-32), clash mask (Docker.py:226,232).
+    None when the hidden width is beyond the kernel's (the caller then applies its module to ``local_features``)."""
+    lib_ = lib or get_lib()
+    H = W1.shape[0]
+    HP = lib_.call("dlpd_hidden_pad", int(H))
+    if HP < 0:
+        return None
+    corr0 = _check(corr0, "corr0", lib)
+    dev = corr0.device
+    P, C0, W = corr0.shape[0], corr0.shape[1], corr0.shape[2]
+    C1 = 0
+    if corr1 is not None:
+        corr1 = _check(corr1, "corr1", lib)
+        C1 = corr1.shape[1]
+    if clash is not None:
+        clash = _check(clash, "clash", lib)
+    if W1.shape[1] != C0 + C1:
+        raise RuntimeError("dlpd: filter width %d does not match %d + %d channels" % (W1.shape[1], C0, C1))
+    W1t = torch.zeros(C0 + C1, HP, dtype=torch.float32, device=dev)
+    W1t[:, :H] = W1.detach().to(dev, torch.float32).t()
+    b1p, W2p = (torch.zeros(HP, dtype=torch.float32, device=dev) for _ in range(2))
+    b1p[:H] = b1.detach().to(dev, torch.float32)
+    W2p[:H] = W2.detach().to(dev, torch.float32).reshape(-1)
+    score = torch.empty(P, W, W, W, dtype=torch.float32, device=dev)
+    best = torch.empty(P, dtype=torch.float32, device=dev)
+    besti = torch.empty(P, dtype=torch.int32, device=dev)
+    T = T.contiguous()
+    lib_.call("dlpd_local_filter", _ptr(corr0), C0, _ptr(corr1), C1, _ptr(clash), _ptr(T), P, int(radius), int(scale),
+              COARSE_MODES[coarse], _ptr(W1t), _ptr(b1p), _ptr(W2p), float(b2.reshape(-1)[0]), HP, 0 if clip is None else 1,
+              float(clip or 0.0), float(threshold), _ptr(score), _ptr(best), _ptr(besti), _stream(dev))
+    return score, best, besti
+
+
+class MultiplyVolumes(nn.Module):
+    """The reference's module (src/Models/MultiplyVolumes.py): ``forward(receptor (B, C, L, L, L), ligand (B, C, L, L, L),
+    T (B, 3))`` -> (B, C), pair i at translation int(T[i]) (truncation toward zero), by the direct-correlation kernel.
+    Inference only; device tensors (``lib=``: the emulated library of the test-suite, host tensors)."""
+
+    def __init__(self, lib=None):
+        super().__init__()
+        self.lib = lib
+
+    def forward(self, receptor, ligand, T):
+        rec, lig = _check(receptor, "receptor", self.lib), _check(ligand, "ligand", self.lib)
+        if rec.dim() != 5 or rec.shape != lig.shape or T.shape[0] != rec.shape[0]:
+            raise RuntimeError("dlpd: MultiplyVolumes expects (B, C, L, L, L) pairs and T (B, 3)")
+        Ti = torch.as_tensor(T).detach().trunc().to(torch.int32).to(rec.device)
+        return local_correlate(rec, lig, Ti, radius=0, scale=1, coarse="trunc", lib=self.lib).reshape(rec.shape[0], rec.shape[1])

@@ -24,7 +24,7 @@
  * Everything else in this header is a VARIANT of one of these stages -- suffix _ext (embedded box), _oriented / _quads (launch
  * variants of the per-channel K1), _form (kernel formulation named: test cross-checks), _occ (occupancy maps: sparse ligands),
  * _aux / un-suffixed (fewer features) -- a stand-alone operator of the plugin surface (dlpd_rotate_trilinear,
- * dlpd_correlate_generic, dlpd_filter_*, dlpd_conv3d*, dlpd_maxpool3d_5s2*), or a size / capability query.  Test hooks
+ * dlpd_correlate_generic, dlpd_local_*, dlpd_filter_*, dlpd_conv3d*, dlpd_maxpool3d_5s2*), or a size / capability query.  Test hooks
  * (dlpd_debug_*) are declared in dlpd_debug.h, not here.
  */
 #ifndef DLPD_H
@@ -206,6 +206,35 @@ int dlpd_generic_box_supported(int L);
 size_t dlpd_correlate_generic_ws_bytes(int nvol, int L);
 int dlpd_correlate_generic(const float* v1, const float* v2, float* out, int nvol, int L, int has_clip, float clip,
                            void* ws, void* stream);
+
+/* LOCAL DOCKING -- MultiplyVolumes (src/Models/MultiplyVolumes.py:13-60) under a rotation, LocalDockingModel.forward
+ * (src/Models/DockingModels.py:102-120; caller LocalTrainer.score, src/Training/LocalTrainer.py:146-177): the per-channel
+ * correlation of the receptor with a ligand under an ARBITRARY rotation at a HANDFUL of translations, by direct summation.
+ *   corr (P, C, W^3)[p,c,d] = sum_x rec[c, x + tau] lig'[c, x],  W = 2r + 1, d in [-r, r]^3, tau = coarse(T_p) + d, zero where
+ *   x + tau leaves the box (so exactly 0 for any |tau_k| >= L); lig' = dlpd_rotate_trilinear(lig, R_p, center), or lig itself
+ *   for R = null.  T (P, 3) int32 signed translations in voxels of the grid of scale * L points per edge;
+ *   coarse(t) = floor(t / scale) (coarse_mode 0: what the global search's nearest upsample, DockingModels.py:74-76, is on the
+ *   wrapped grid -- corr is then that search's correlation volume at (T_p + scale d) mod 2 scale L) or trunc(t / scale)
+ *   (coarse_mode 1: the int() of MultiplyVolumes.py:56-58).
+ * rec, lig (C, L^3) with per-pose strides in floats (0: one set for all poses); any 2 <= L <= 128, any C, 0 <= r <= 3.
+ * ws: dlpd_local_ws_bytes(P, C, L, r) bytes (per-block partial sums, added in a fixed order: bit-reproducible). */
+size_t dlpd_local_ws_bytes(int P, int C, int L, int r);
+/* poses ONE dlpd_local_correlate call takes at most (a launch holds < 2^32 threads: one block per pose, channel and slab of
+ * x-planes); more is DLPD_ERR_UNSUPPORTED -- the caller batches.  0 for an unsupported shape. */
+int dlpd_local_max_poses(int C, int L);
+int dlpd_local_correlate(const float* rec, const float* lig, const float* R, const int* T, float* corr, void* ws, int P, int C,
+                         int L, int r, int scale, int coarse_mode, float center, long long rec_pstride, long long lig_pstride,
+                         void* stream);
+/* The filter of those poses (DockingModels.py:118-119; with clip / clash the search's DockingModels.py:74-83, Docker.py:226,232):
+ * feat[d] = [clamp(corr0[:, d]), clamp(corr1[:, coarse(T_p + d) - coarse(T_p)])], score (P, W^3) = MLP(feat) * (clash < thr).
+ * corr0 (P, C0, W^3) from dlpd_local_correlate(scale 1, r); corr1 (P, C1, Wc^3) from dlpd_local_correlate(scale, rc)
+ * on the coarse grid, rc = (r + 1) / 2 for scale 2 and r for scale 1, or null; clash (P, W^3) the forbidden volumes' correlation, or null; T on the FINE grid; scale 1 or 2.
+ * W1t (C0 + C1, HP), b1 (HP), W2 (HP) padded to HP = dlpd_hidden_pad(H); a wider filter is DLPD_ERR_UNSUPPORTED (the caller
+ * applies its module to the features).  best_score / best_index (P; either may be null): the minimum of each pose's window
+ * and its flat index, lowest index on a tie (torch.min in Docker.update_top, Docker.py:89-98). */
+int dlpd_local_filter(const float* corr0, int C0, const float* corr1, int C1, const float* clash, const int* T, int P, int r,
+                      int scale, int coarse_mode, const float* W1t, const float* b1, const float* W2, float b2, int HP,
+                      int has_clip, float clip, float thr, float* score, float* best_score, int* best_index, void* stream);
 
 /* Stage K3, plain: real correlation volumes out (nb, CT, N^3) [+ clamp to +-clip]
  * (output of VolumeConvolution(clip), DockingModels.py:48,71). */

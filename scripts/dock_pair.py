@@ -3,6 +3,9 @@ without the benchmark table: representation -> exhaustive rotation x translation
 
     python scripts/dock_pair.py receptor.pdb ligand.pdb -out pair.dat [-group SE3|E3] [-angle_inc 15]
         [-experiment DIR -load_epoch N]    # optional trained weights (GlobalDockingModel.load)
+        [--refine ANGLE[:STEPS[:RADIUS]]]  # SE3: refine the top list over off-set rotations (ANGLE degrees on a
+                                           # (2 STEPS + 1)^3 axis-angle lattice, default 1) and translations within
+                                           # RADIUS voxels (default 1) -> <out>.refined.dat beside the .dat
 
 Multi-GPU: launch with torch.distributed.run; rotations are sharded over the ranks, rank 0 writes."""
 import argparse
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("-batch_size", default=16, type=int)
     ap.add_argument("-experiment", default=None)
     ap.add_argument("-load_epoch", default=0, type=int)
+    ap.add_argument("--refine", default=None, metavar="ANGLE[:STEPS[:RADIUS]]")
     args = ap.parse_args()
     entry.build()
     from deeplocalproteindocking_amd.Docker import Docker
@@ -53,11 +57,27 @@ def main():
                     max_conf=args.max_conf, device=dev, coords_backend=CoordsBackend(), rank=rank, world_size=world)
     if rank == 0:
         docker.new_log(args.out, rewrite=True)
+    refine = None
+    if args.refine is not None:
+        if args.group != "SE3":
+            ap.error("--refine needs -group SE3 (the ligand's volumes are rotated, not re-represented)")
+        part = args.refine.split(":")
+        refine = (float(part[0]), int(part[1]) if len(part) > 1 else 1, int(part[2]) if len(part) > 2 else 1)
     with torch.no_grad():
-        (docker.dockSE3 if args.group == "SE3" else docker.dockE3)(args.receptor, args.ligand, args.batch_size)
+        prepared = docker.prepare(args.receptor, args.ligand, "SE3") if refine else None
+        (docker.dockSE3 if args.group == "SE3" else docker.dockE3)(args.receptor, args.ligand, args.batch_size, prepared=prepared)
     docker.cleanup()
     if rank == 0:
         print("wrote", args.out, "(%d poses, best score %f)" % (len(docker.top_list), docker.top_list[0][4]))
+    if refine:
+        from deeplocalproteindocking_amd.Utils.Rotations import local_perturbations
+        docker.refine_prepared(prepared, perturbations=local_perturbations(refine[0], refine[1]), radius=refine[2])
+        if rank == 0:           # every rank refined the same gathered list
+            name = (args.out[:-4] if args.out.endswith(".dat") else args.out) + ".refined.dat"
+            docker.new_log(name, rewrite=True)
+            docker.write_refined_conformations()
+            docker.cleanup()
+            print("wrote", name, "(%d poses, best score %f)" % (len(docker.refined_list), docker.refined_list[0][2]))
     if world > 1:
         dist.destroy_process_group()
 

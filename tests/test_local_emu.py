@@ -1,0 +1,462 @@
+"""Local docking (csrc/dlpd_local.h: direct correlation at given poses, its filter; ops.MultiplyVolumes, LocalDockingModel,
+Docker.score_poses / refine) on the CPU-emulated kernel library, against the oracle and the fixtures G1 / G8.
+
+Tolerances are derived, not chosen: a correlation value is an f32 sum of K products in some order on both sides, so
+|got - want| <= 2 (K + 1) 2^-24 sum|v1 v2| (the sum taken in float64 here); where a trilinear rotation is involved the
+repository's parity band is added: 1e-4 of the largest value compared (BASELINE.json; TOL in test_gpu_parity.py)."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import docking_oracle as orc
+
+TOL = 1e-4
+EPS = 2.0 ** -24
+
+
+def _signed_index(t, N):
+    return tuple(int(v) % N for v in t)
+
+
+def _window(r):
+    return [(dx, dy, dz) for dx in range(-r, r + 1) for dy in range(-r, r + 1) for dz in range(-r, r + 1)]
+
+
+def _rots(n, seed=1):
+    ang = np.random.RandomState(seed).uniform(-np.pi, np.pi, size=(n, 3))
+    return orc.euler_to_matrix(ang[:, 0], np.abs(ang[:, 1]), ang[:, 2])
+
+
+# ---------------------------------------------------------------------------------------------- 1: MultiplyVolumes vs G1
+def test_multiply_volumes_reproduces_the_reference_module(golden, emu):
+    from deeplocalproteindocking_amd.ops import MultiplyVolumes
+    g = golden("g1_multiply_volumes.npz")
+    mv = MultiplyVolumes(lib=emu)
+    for L, count in ((4, 343), (6, 1331)):
+        v1, v2 = torch.from_numpy(g["v1_L%d" % L]), torch.from_numpy(g["v2_L%d" % L])
+        T = torch.from_numpy(g["T_L%d" % L]).float()
+        assert T.shape[0] == count
+        B = T.shape[0]
+        got = mv(v1.expand(B, -1, -1, -1, -1).contiguous(), v2.expand(B, -1, -1, -1, -1).contiguous(), T).numpy()
+        mag = orc.correlate_direct(np.abs(v1.numpy()), np.abs(v2.numpy()))[0]                 # sum |v1 v2| per translation
+        N = 2 * L
+        bound = np.stack([mag[(slice(None),) + _signed_index(t, N)] for t in g["T_L%d" % L]]) * 2 * (L ** 3 + 1) * EPS
+        assert got.shape == g["out_L%d" % L].shape
+        assert (np.abs(got - g["out_L%d" % L]) <= bound).all()
+        assert np.abs(g["out_L%d" % L]).max() > 1.0
+    # fractional rows: int() truncates toward zero
+    v1 = torch.from_numpy(g["v1_L6"]).repeat(2, 1, 1, 1, 1)
+    v2 = torch.from_numpy(g["v2_L6"]).repeat(2, 1, 1, 1, 1)
+    got = mv(v1, v2, torch.from_numpy(g["Tfrac"])).numpy()
+    mag = orc.correlate_direct(np.abs(g["v1_L6"]), np.abs(g["v2_L6"]))[0]
+    tt = np.trunc(g["Tfrac"]).astype(int)
+    bound = np.stack([mag[(slice(None),) + _signed_index(t, 12)] for t in tt]) * 2 * (6 ** 3 + 1) * EPS
+    assert (np.abs(got - g["out_frac"]) <= bound).all()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        MultiplyVolumes()(v1, v2, torch.zeros(2, 3))
+
+
+# ---------------------------------------------------------------------------------------------- 2: dlpd_local_correlate
+def _correlate_case(emu, L, C, r, seed):
+    from deeplocalproteindocking_amd import ops
+    g = torch.Generator().manual_seed(seed)
+    rec, lig = torch.randn(C, L, L, L, generator=g), torch.randn(C, L, L, L, generator=g)
+    P = 5
+    R = torch.from_numpy(_rots(P, seed=seed)).float().contiguous()
+    T = torch.randint(-(L - 1), L, (P, 3), generator=g).int()
+    T[0] = torch.tensor([L - 1, -(L - 1), 0])          # part of the window at and beyond |tau| = L - 1
+    T[1] = torch.tensor([L, 2, -L - 1])                # ... and a centre beyond the box
+    T[2] = torch.tensor([-(L - 2), L - 1 - r, 1])
+    return rec, lig, R, T, ops.local_correlate(rec, lig, T, R=R, radius=r, lib=emu)
+
+
+@pytest.mark.parametrize("L,C,r", [(6, 3, 0), (9, 2, 1), (12, 2, 2), (9, 2, 3), (6, 1, 3), (12, 3, 1)])
+def test_local_correlate_matches_oracle(emu, L, C, r):
+    rec, lig, R, T, got = _correlate_case(emu, L, C, r, seed=10 * L + r)
+    N, W = 2 * L, 2 * r + 1
+    assert tuple(got.shape) == (T.shape[0], C, W, W, W)
+    worst = 0.0
+    for p in range(T.shape[0]):
+        lr = orc.rotate_volume(lig[None], R[p:p + 1])
+        full = orc.correlate_direct(rec[None].numpy(), lr.numpy())[0]
+        mag = orc.correlate_direct(np.abs(rec[None].numpy()), np.abs(lr.numpy()))[0]
+        scale = np.abs(full).max()
+        for d in _window(r):
+            t = T[p].numpy() + np.array(d)
+            mine = got[p, :, d[0] + r, d[1] + r, d[2] + r].numpy()
+            if (np.abs(t) >= L).any():
+                assert (mine == 0.0).all()              # no overlap: exactly zero
+                continue
+            idx = (slice(None),) + _signed_index(t, N)
+            bound = 2 * (L ** 3 + 1) * EPS * mag[idx] + TOL * scale
+            assert (np.abs(mine - full[idx]) <= bound).all(), (p, d, mine, full[idx])
+            worst = max(worst, float(np.abs(mine - full[idx]).max() / scale))
+    print("local_correlate L=%d C=%d r=%d: worst error %.3g of max|corr|" % (L, C, r, worst))
+
+
+def test_local_correlate_given_volumes_per_pose_and_coarse_modes(emu):
+    """R = null (volumes as they are), one volume pair per pose, and the two coarse conventions on a half-resolution grid."""
+    from deeplocalproteindocking_amd import ops
+    L, C, P = 6, 2, 6
+    g = torch.Generator().manual_seed(77)
+    rec, lig = torch.randn(P, C, L, L, L, generator=g), torch.randn(P, C, L, L, L, generator=g)
+    T = torch.tensor([[-3, 5, -1], [-7, 3, 9], [1, -1, -5], [0, 0, 0], [-11, 11, -9], [-1, 1, -3]], dtype=torch.int32)
+    for mode, fn in (("floor", np.floor), ("trunc", np.trunc)):
+        got = ops.local_correlate(rec, lig, T, radius=0, scale=2, coarse=mode, lib=emu).reshape(P, C)
+        for p in range(P):
+            t = fn(T[p].numpy() / 2.0).astype(int)
+            full = orc.correlate_direct(rec[p:p + 1].numpy(), lig[p:p + 1].numpy())[0]
+            mag = orc.correlate_direct(np.abs(rec[p:p + 1].numpy()), np.abs(lig[p:p + 1].numpy()))[0]
+            idx = (slice(None),) + _signed_index(t, 2 * L)
+            want = full[idx] if (np.abs(t) < L).all() else np.zeros(C)
+            assert (np.abs(got[p].numpy() - want) <= 2 * (L ** 3 + 1) * EPS * mag[idx]).all()
+    a = ops.local_correlate(rec, lig, T, radius=0, scale=2, coarse="floor", lib=emu)
+    b = ops.local_correlate(rec, lig, T, radius=0, scale=2, coarse="trunc", lib=emu)
+    assert not torch.equal(a, b)                        # negative odd components tell the two apart
+
+
+def test_local_correlate_launch_grid_limit(emu):
+    """A launch holds fewer than 2^32 threads, i.e. 2^24 - 1 blocks of 256: one block per pose, channel and slab of x-planes."""
+    assert emu.call("dlpd_local_max_poses", 16, 80) == (2 ** 32 - 1) // 256 // (16 * 27) == 38836
+    assert emu.call("dlpd_local_max_poses", 32, 40) == (2 ** 32 - 1) // 256 // (32 * 7)
+    assert emu.call("dlpd_local_max_poses", 1, 129) == 0 == emu.call("dlpd_local_max_poses", 0, 8)
+    x = torch.zeros(8)                                   # (refused before anything is read)
+    with pytest.raises(RuntimeError, match="UNSUPPORTED"):
+        emu.call("dlpd_local_correlate", x.data_ptr(), x.data_ptr(), None, x.data_ptr(), x.data_ptr(), x.data_ptr(), 38837, 16, 80, 0, 1, 0,
+                 40.0, 0, 0, 0)
+
+
+# ---------------------------------------------------------------------------------------------- 3: Docker.score_poses
+def _model(sizes, thr, clip, emu, seed=3):
+    from deeplocalproteindocking_amd.Models import GlobalDockingModel, SimpleFilter
+    torch.manual_seed(seed)
+    filt = SimpleFilter(sizes)
+    with torch.no_grad():
+        filt.fc[0].bias.normal_(0.0, 0.3)
+        filt.fc[2].bias.normal_(0.0, 0.3)
+    return GlobalDockingModel(None, filt, threshold_clash=thr, clip=clip, lib=emu).eval(), [w.detach() for w in filt.parameters_tuple()]
+
+
+def _volumes(sizes, L, seed, amp):
+    g = torch.Generator().manual_seed(seed)
+    rec = [torch.randn(1, c, L >> i, L >> i, L >> i, generator=g) * amp for i, c in enumerate(sizes)]
+    lig = [torch.randn(1, c, L >> i, L >> i, L >> i, generator=g) * amp for i, c in enumerate(sizes)]
+    recf, ligf = torch.rand(L, L, L, generator=g), torch.rand(L, L, L, generator=g)
+    return rec, lig, recf, ligf
+
+
+def _oracle_volume(rec, lig, recf, ligf, W, R1, thr, clip):
+    """The global search's V for one rotation (oracle.score_volumes x oracle.clash_mask) and the clash correlation."""
+    Rb = torch.from_numpy(np.asarray(R1, dtype=np.float64)[None]).float()
+    lr = [orc.rotate_volume(v, Rb) for v in lig]
+    mask, norm = orc.clash_mask(recf[None, None], orc.rotate_volume(ligf[None, None], Rb), thr)
+    return (mask * orc.score_volumes(rec, lr, *W, clip=clip))[0], norm[0]
+
+
+@pytest.mark.parametrize("sizes,clip,seed,r", [([4], 5.0, 41, 1), ([4], 0.8, 42, 1), ([4, 6], 5.0, 43, 1), ([4, 6], 0.8, 44, 1),
+                                               ([4, 6], 0.8, 46, 2), ([4, 6], 5.0, 47, 3), ([4, 6], 0.8, 48, 0)])
+def test_score_poses_matches_the_global_search_oracle(emu, sizes, clip, seed, r):
+    """Every radius with two resolutions: the coarse window (radius (r + 1) / 2) and its index coarse(t + d) - coarse(t) are
+    checked against the oracle's upsampled volume, not against a restatement of the same formula."""
+    from deeplocalproteindocking_amd.Docker import Docker
+    L = 8
+    thr = 0.25 * L ** 3 * 0.5
+    model, W = _model(sizes, thr, clip, emu)
+    rec, lig, recf, ligf = _volumes(sizes, L, seed, amp=0.6)
+    R = _rots(6, seed=seed)
+    # negative odd components: floor != trunc; the last two overlap enough for the clash mask to bite
+    T = np.array([[-3, 5, -1], [-5, -1, 3], [1, -7, -3], [2, 0, -5], [1, -1, 1], [-1, 1, -3]])
+    # the whole window inside |tau| <= L: beyond it the search's grid wraps (index (t + d) mod 2L is ANOTHER translation there),
+    # while a local correlation is zero -- not a comparison the two share
+    T = np.clip(T, -(L - r), L - r)
+    dk = Docker(model, box_size=L, max_conf=10, rotations=R, device="cpu", lib=emu)
+    got = dk.score_poses(rec, lig, R, T, recf, ligf, radius=r).numpy()
+    assert got.shape == (6, 2 * r + 1, 2 * r + 1, 2 * r + 1)
+    N = 2 * L
+    compared = skipped = nonzero = 0
+    worst = 0.0
+    for p in range(6):
+        Vo, norm = _oracle_volume(rec, lig, recf, ligf, W, R[p], thr, clip)
+        band = TOL * float(Vo.abs().max())
+        for d in _window(r):
+            idx = _signed_index(T[p] + np.array(d), N)
+            if abs(float(norm[idx]) - thr) <= 1e-3 * thr:
+                skipped += 1
+                continue
+            compared += 1
+            nonzero += float(Vo[idx]) != 0.0
+            err = abs(float(got[p, d[0] + r, d[1] + r, d[2] + r]) - float(Vo[idx]))
+            worst = max(worst, err / band)
+            assert err <= band, (p, d, got[p, d[0] + r, d[1] + r, d[2] + r], float(Vo[idx]))
+    print("score_poses %s clip %s: worst error %.3g of the band, %d skipped, %d / %d non-zero" % (sizes, clip, worst, skipped, nonzero, compared))
+    assert skipped <= 0.01 * (compared + skipped)
+    assert 0.3 * compared <= nonzero < compared        # the mask is exercised, and most scores are not zeros
+    if clip < 1.0:                                     # the clip bites: without it the scores differ
+        model.clip = 5.0
+        assert np.abs(dk.score_poses(rec, lig, R, T, recf, ligf, radius=r).numpy() - got).max() > 10 * band
+
+
+def test_score_poses_with_a_clash_provider_equals_the_stored_forbidden_volume(emu):
+    """The clash channel from a provider of per-pose volumes (Docker.py:221-224: re-projected atoms; here a stub that hands
+    back the rotated forbidden volume) against the path that rotates the stored volume itself: the same scores, also when the
+    provider's volumes make score_poses split the poses into batches; the model comes back in the mode it went in."""
+    from deeplocalproteindocking_amd.Docker import Docker
+    L, sizes = 8, [4, 6]
+    thr = 0.25 * L ** 3 * 0.5
+    model, W = _model(sizes, thr, 0.8, emu)
+    rec, lig, recf, ligf = _volumes(sizes, L, 49, amp=0.6)
+    R = _rots(5, seed=49)
+    T = np.array([[-3, 5, -1], [1, -1, 1], [-1, 1, -3], [2, 0, -5], [0, 1, 0]])
+    dk = Docker(model, box_size=L, max_conf=10, rotations=R, device="cpu", lib=emu)
+    want = dk.score_poses(rec, lig, R, T, recf, ligf, radius=1)
+    calls = []
+
+    def provider(Rb):
+        calls.append(Rb.shape[0])
+        return dk.vol_rotate(ligf[None, None].expand(Rb.shape[0], -1, -1, -1, -1).contiguous(), Rb.contiguous())
+    got = dk.score_poses(rec, lig, R, T, recf, None, clash_provider=provider, radius=1)
+    assert calls == [5] and got.numpy().tobytes() == want.numpy().tobytes()
+    assert (want == 0).any() and (want != 0).any()
+    import importlib
+    D = importlib.import_module("deeplocalproteindocking_amd.Docker.Docker")          # (the module; the package exports the class)
+    old, calls[:] = D.PROVIDER_BATCH_BYTES, []
+    D.PROVIDER_BATCH_BYTES = 2 * 4 * L ** 3              # room for two poses' volumes
+    try:
+        got = dk.score_poses(rec, lig, R, T, recf, None, clash_provider=provider, radius=1)
+    finally:
+        D.PROVIDER_BATCH_BYTES = old
+    assert calls == [2, 2, 1] and got.numpy().tobytes() == want.numpy().tobytes()
+    with pytest.raises(Exception, match="ligand_forbidden or clash_provider"):
+        dk.score_poses(rec, lig, R, T, recf)
+    model.train()
+    dk.score_poses(rec, lig, R[:1], T[:1])
+    assert model.training
+    model.eval()
+    dk.score_poses(rec, lig, R[:1], T[:1])
+    assert not model.training
+
+
+def test_refine_prepared_from_pdb_files_follows_the_search(emu, tmp_path):
+    """prepare -> dockSE3(prepared=) -> refine_prepared, as scripts/dock_pair.py --refine runs them: the clash channel comes
+    from the re-projected ligand atoms in the search and in the refinement alike, so the search's poses re-scored at their
+    own rotation and translation get their scores back, and no refined pose is worse than its source."""
+    from test_atoms import _tiny_model, write_fake_pdb
+    from deeplocalproteindocking_amd.Docker import Docker
+    from deeplocalproteindocking_amd.Utils.FullAtom import CoordsBackend
+    from deeplocalproteindocking_amd.Utils.Rotations import local_perturbations
+    frec, flig = str(tmp_path / "r.pdb"), str(tmp_path / "l.pdb")
+    write_fake_pdb(frec, 14, 5)
+    write_fake_pdb(flig, 9, 6)
+    L, K = 32, 6
+    R = orc.euler_to_matrix(0.3 + 0.03 * np.arange(2), 1.1 - 0.02 * np.arange(2), -2.0 + 0.025 * np.arange(2))
+    dk = Docker(_tiny_model(), box_size=L, resolution=1.25, max_conf=K, rotations=R, device="cpu", lib=emu,
+                coords_backend=CoordsBackend(lib=emu))
+    with torch.no_grad():
+        p = dk.prepare(frec, flig, "SE3")
+        dk.dockSE3(frec, flig, batch_size=2, prepared=p)
+        top = list(dk.top_list)
+        assert len(top) == K and top[0][4] < 0
+        Q = local_perturbations(4.0, 1)[:3]
+        refined = dk.refine_prepared(p, perturbations=Q, radius=1)
+        again = dk.refine_prepared(p, perturbations=Q[:1], radius=0)          # identity, d = 0: the re-scored list itself
+    assert dk.top_list == top and len(refined) == K
+    band = TOL * max(abs(e[4]) for e in top)             # <= max|V|: a stricter band than the stated one
+    for Rm, tt, score, n in again:
+        assert tt == dk.signed_translation(*top[n][1:4]) and abs(score - top[n][4]) <= band
+    rescored = {n: score for _, _, score, n in again}
+    for Rm, tt, score, n in refined:
+        assert score <= rescored[n] + band
+    dk.new_log(str(tmp_path / "pair.refined.dat"))
+    dk.write_refined_conformations()
+    dk.cleanup()
+    assert len(open(str(tmp_path / "pair.refined.dat")).read().strip().split("\n")) == K
+    with pytest.raises(Exception, match="SE3 pairs only"):
+        p.group = "E3"
+        dk.refine_prepared(p)
+
+
+def test_score_poses_calls_any_other_filter_on_the_features(emu):
+    """A filter that is not the reference MLP is called on the (poses x window, channels) rows."""
+    from deeplocalproteindocking_amd.Docker import Docker
+    from deeplocalproteindocking_amd.Models import GlobalDockingModel
+    L, sizes, thr = 8, [4, 6], 64.0
+    model, W = _model(sizes, thr, 0.8, emu)
+    rec, lig, recf, ligf = _volumes(sizes, L, 45, amp=0.6)
+    R, T = _rots(2, seed=9), np.array([[-3, 5, -1], [1, -1, 2]])
+    dk = Docker(model, box_size=L, max_conf=10, rotations=R, device="cpu", lib=emu)
+    want = dk.score_poses(rec, lig, R, T, recf, ligf, radius=1)
+
+    class Wrapped(torch.nn.Module):
+        def __init__(self, inner):
+            super().__init__()
+            self.inner = inner
+
+        def forward(self, x):
+            return self.inner(x)
+    other = GlobalDockingModel(None, Wrapped(model.filter), threshold_clash=thr, clip=0.8, lib=emu).eval()
+    got = Docker(other, box_size=L, max_conf=10, rotations=R, device="cpu", lib=emu).score_poses(rec, lig, R, T, recf, ligf, radius=1)
+    assert (got - want).abs().max() <= 1e-5 * want.abs().max()
+
+
+def test_local_filter_minimum_per_pose_lowest_index_wins_a_tie(emu):
+    """dlpd_local_filter's per-pose minimum against numpy on the scores it wrote (argmin: first occurrence), with windows of
+    more voxels than a wave has lanes, ties among masked (zero) scores, and a filter too wide for the kernel."""
+    from deeplocalproteindocking_amd import ops
+    g = torch.Generator().manual_seed(8)
+    P, C0, C1, r = 5, 3, 2, 2
+    W = 2 * r + 1
+    corr0, corr1 = torch.randn(P, C0, W, W, W, generator=g), torch.randn(P, C1, 3, 3, 3, generator=g)
+    clash = torch.rand(P, W, W, W, generator=g)
+    clash[1] = 2.0                                       # every voxel of pose 1 masked: all scores 0, index 0 wins
+    T = torch.tensor([[-3, 5, -1], [0, 0, 0], [1, -1, 7], [-7, -7, -7], [2, 4, 6]], dtype=torch.int32)
+    W1, b1 = torch.randn(2, C0 + C1, generator=g), torch.randn(2, generator=g)
+    W2, b2 = -torch.rand(1, 2, generator=g), torch.tensor([0.5])
+    score, best, besti = ops.local_filter(corr0, corr1, clash, T, r, W1, b1, W2, b2, scale=2, clip=0.7, threshold=0.6, lib=emu)
+    feat = ops.local_features(corr0, corr1, T, r, scale=2, clip=0.7)
+    want = (orc.filter_mlp(feat, W1, b1, W2, b2).reshape(P, W, W, W) * (clash < 0.6).float()).numpy()
+    assert np.abs(score.numpy() - want).max() <= 1e-6 * np.abs(want).max()
+    flat = score.numpy().reshape(P, -1)
+    assert besti.tolist() == np.argmin(flat, axis=1).tolist() and besti[1] == 0
+    assert best.numpy().tobytes() == flat[np.arange(P), np.argmin(flat, axis=1)].tobytes()
+    assert (flat == 0).any() and (flat < 0).any()
+    wide = ops.local_filter(corr0, corr1, clash, T, r, torch.randn(40, C0 + C1), torch.randn(40), torch.randn(1, 40), b2, scale=2, lib=emu)
+    assert wide is None                                   # hidden width beyond the kernel's: the caller applies its module
+
+
+# ---------------------------------------------------------------------------------------------- 4: LocalDockingModel vs G8
+def _g8():
+    from conftest import GOLDEN
+    return np.load(os.path.join(GOLDEN, "local", "g8_local_forward.npz"))
+
+
+def _g8_filter(g):
+    from deeplocalproteindocking_amd.Models import SimpleFilter
+    filt = SimpleFilter(g["num_outputs"].tolist())
+    keys = json.loads(bytes(g["filter_keys"]).decode())
+    assert list(filt.state_dict().keys()) == keys
+    filt.load_state_dict({k: torch.from_numpy(g["filter_sd_" + k]) for k in keys}, strict=True)
+    return filt.eval()
+
+
+def test_local_docking_model_reproduces_the_reference_forward(emu):
+    from deeplocalproteindocking_amd.Models import E3MultiResRepr4x4, LocalDockingModel
+    g = _g8()
+    rec, lig, T = torch.from_numpy(g["receptor"]), torch.from_numpy(g["ligand"]), torch.from_numpy(g["T"])
+    want = g["out"]
+    band = TOL * np.abs(want).max()
+    assert (np.abs(T.numpy()) >= rec.shape[2]).any() and (T.numpy() != np.trunc(T.numpy())).any()
+
+    class Recorded(torch.nn.Module):                     # isolates the new kernels and the trunc convention
+        def forward(self, x):
+            tag = "rec" if x is rec else "lig"
+            return [torch.from_numpy(g["%s_vol%d" % (tag, i)]) for i in range(2)]
+    stub = LocalDockingModel(Recorded(), _g8_filter(g), lib=emu).eval()
+    with torch.no_grad():
+        got = stub(rec, lig, T).numpy()
+    print("LocalDockingModel (recorded volumes): max error %.3g, band %.3g" % (np.abs(got - want).max(), band))
+    assert got.shape == want.shape == (rec.shape[0], 1)
+    assert np.abs(got - want).max() <= band
+    # the whole call: this build's representation with the recorded weights
+    net = E3MultiResRepr4x4(multiplier=1).eval()
+    keys = json.loads(bytes(g["repr_keys"]).decode())
+    net.load_state_dict({k: torch.from_numpy(g["repr_sd_" + k]) for k in keys}, strict=True)
+    model = LocalDockingModel(net, _g8_filter(g), lib=emu).eval()
+    with torch.no_grad():
+        got = model(rec, lig, T).numpy()
+    print("LocalDockingModel (whole call): max error %.3g, band %.3g" % (np.abs(got - want).max(), band))
+    assert np.abs(got - want).max() <= band
+    # inference only: refuses to run where a graph would be expected
+    with pytest.raises(RuntimeError, match="inference only"):
+        model(rec, lig, T)
+    # save / load with the reference's file names
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        model.save(td, 3, model_name="M")
+        assert sorted(os.listdir(td)) == ["M_filter_epoch3.th", "M_repr_epoch3.th"]
+        model.load(td, 3, model_name="M")
+
+
+# ---------------------------------------------------------------------------------------------- 5: Docker.refine
+def _refine_case(emu):
+    from deeplocalproteindocking_amd.Docker import Docker
+    from deeplocalproteindocking_amd.Utils.Rotations import local_perturbations
+    L, sizes, clip = 8, [3], 5.0
+    thr = 0.25 * L ** 3 * 0.5
+    model, W = _model(sizes, thr, clip, emu, seed=5)
+    rec, lig, recf, ligf = _volumes(sizes, L, 51, amp=0.6)
+    R = _rots(3, seed=52)
+    dk = Docker(model, box_size=L, max_conf=10, rotations=R, device="cpu", lib=emu)
+    poses = [(0, 3, 13, 1, 0.0), (2, 15, 2, 11, 0.0), (1, 0, 5, 14, 0.0)]
+    Q = local_perturbations(10.0, 1)
+    refined = dk.refine(rec, lig, recf, ligf, poses=poses, perturbations=Q, radius=1)
+    return dk, (rec, lig, recf, ligf, W, thr, clip), R, poses, Q, refined
+
+
+def test_local_perturbations_are_deterministic_rotations_identity_first():
+    from deeplocalproteindocking_amd.Utils.Rotations import local_perturbations
+    Q = local_perturbations(5.0, 1)
+    assert Q.shape == (27, 3, 3) and Q.dtype == torch.float64 and torch.equal(Q[0], torch.eye(3, dtype=torch.float64))
+    assert (Q @ Q.transpose(1, 2) - torch.eye(3, dtype=torch.float64)).abs().max() < 1e-14
+    assert (torch.linalg.det(Q) - 1).abs().max() < 1e-14
+    ang = torch.rad2deg(torch.acos(((Q.diagonal(dim1=1, dim2=2).sum(1) - 1) / 2).clamp(-1, 1)))
+    assert abs(float(ang.max()) - 5.0 * 3 ** 0.5) < 1e-9 and torch.equal(Q, local_perturbations(5.0, 1))
+    assert local_perturbations(2.0, 2).shape[0] == 125
+
+
+def test_refine_matches_brute_force_over_the_oracle(emu, tmp_path):
+    dk, (rec, lig, recf, ligf, W, thr, clip), R, poses, Q, refined = _refine_case(emu)
+    L, N, r = 8, 16, 1
+    assert dk.top_list == [] and len(refined) == len(poses)
+    assert [e[2] for e in refined] == sorted(e[2] for e in refined)
+    rescored = dk.score_poses(rec, lig, R[[p[0] for p in poses]], [dk.signed_translation(*p[1:4]) for p in poses], recf, ligf)
+    for Rm, tt, score, n in refined:
+        i, x, y, z, _ = poses[n]
+        t0 = np.array(dk.signed_translation(x, y, z))
+        best, table, scale = None, {}, 0.0
+        for q in range(Q.shape[0]):
+            Rq = Q[q].numpy() @ R[i]
+            Vo, norm = _oracle_volume(rec, lig, recf, ligf, W, Rq, thr, clip)
+            scale = max(scale, float(Vo.abs().max()))
+            for d in _window(r):
+                idx = _signed_index(t0 + np.array(d), N)
+                table[(q, d)] = (float(Vo[idx]), abs(float(norm[idx]) - thr) <= 1e-3 * thr)
+                if best is None or table[(q, d)][0] < table[best][0]:
+                    best = (q, d)
+        band = TOL * scale
+        q_got = [q for q in range(Q.shape[0]) if np.abs(Q[q].numpy() @ R[i] - Rm).max() < 1e-12]
+        assert len(q_got) >= 1
+        d_got = tuple(int(v) for v in np.array(tt) - t0)
+        key = (q_got[0], d_got)
+        assert max(abs(v) for v in d_got) <= r
+        if not table[key][1]:
+            assert abs(score - table[key][0]) <= band                      # the refined score is the oracle's at that pose
+        if key != best and not (table[key][1] or table[best][1]):
+            assert abs(table[key][0] - table[best][0]) <= band, (key, best, table[key], table[best])
+        assert score <= float(rescored[n, 0, 0, 0]) + band                 # never worse than the re-scored input
+    # .dat round trip through the consumer
+    from deeplocalproteindocking_amd.Results.DockerParser import DockerParser
+    dk.new_log(str(tmp_path / "T1.dat"))
+    dk.write_refined_conformations()
+    dk.cleanup()
+    text = open(str(tmp_path / "T1.dat")).read()
+    assert all(len(line.split("\t")) == 13 for line in text.strip().split("\n"))
+    confs = DockerParser(str(tmp_path), coords_backend=object()).parse_output("T1")["conformations"]
+    assert len(confs) == len(refined)
+    for (rot, t, s), (Rm, tt, score, _) in zip(confs, refined):
+        assert (rot[0].numpy() - Rm).__abs__().max() < 1e-6 and abs(s - score) < 1e-6
+        assert t[0].tolist() == [float(int(v * dk.resolution)) for v in tt]
+
+
+# ---------------------------------------------------------------------------------------------- 6: run-to-run identity
+def test_local_kernels_are_bit_reproducible(emu):
+    a = _correlate_case(emu, 9, 2, 1, seed=5)[4]
+    b = _correlate_case(emu, 9, 2, 1, seed=5)[4]
+    assert a.numpy().tobytes() == b.numpy().tobytes()
+    ra, rb = _refine_case(emu)[5], _refine_case(emu)[5]
+    assert len(ra) == len(rb)
+    for x, y in zip(ra, rb):
+        assert x[0].tobytes() == y[0].tobytes() and x[1] == y[1] and x[3] == y[3]
+        assert np.float32(x[2]).tobytes() == np.float32(y[2]).tobytes()
