@@ -126,25 +126,31 @@ class LocalDockingModel(nn.Module):
     surface: ``.representation``, ``.filter``, ``.mult``, ``save`` / ``load`` with the reference's file names,
     ``forward(receptor, ligand, T)`` -> (B, 1).
 
-    INFERENCE ONLY: the correlation runs in a HIP kernel without a backward.  ``forward`` raises when autograd is enabled and a
-    parameter requires a gradient (call it under ``torch.no_grad()``), rather than return a tensor that silently has no graph.
+    ``differentiable=False`` (the default) is INFERENCE ONLY: ``forward`` raises when autograd is enabled and a parameter
+    requires a gradient (call it under ``torch.no_grad()``), rather than return a tensor that silently has no graph.
+    ``differentiable=True`` (a public attribute; ``Training.LocalTrainer`` sets it on the model it is given) is the model that
+    is trained: under autograd the correlation goes through the differentiable ``MultiplyVolumes`` (the adjoint kernel of
+    csrc/dlpd_local_grad.h), the representation runs as the plain torch modules it is made of, and the filter is CALLED -- the
+    fused filter kernel has no graph and serves ``torch.no_grad()`` only, as before.
     A filter that is not the reference's MLP (or is wider than the kernel's hidden widths) is called on the (B, sum C) features."""
     FILES = GlobalDockingModel.FILES
 
-    def __init__(self, representation, filter, lib=None):
+    def __init__(self, representation, filter, lib=None, differentiable=False):
         super().__init__()
         self.representation, self.filter = representation, filter
         self.mult = MultiplyVolumes(lib=lib)
         self._lib = lib
+        self.differentiable = bool(differentiable)
 
     _paths = GlobalDockingModel._paths
     save = GlobalDockingModel.save
     load = GlobalDockingModel.load
 
     def forward(self, receptor, ligand, T):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if graph and not self.differentiable:
             raise RuntimeError("dlpd: LocalDockingModel is inference only (no backward through the correlation kernel): "
-                               "call it under torch.no_grad()")
+                               "call it under torch.no_grad(), or construct it with differentiable=True")
         edge = float(receptor.shape[2])
         # one correlation value per channel of every resolution: T lives on the input grid, each resolution reads it
         # scaled to its own edge (MultiplyVolumes truncates the scaled value toward zero)
@@ -152,7 +158,7 @@ class LocalDockingModel(nn.Module):
         # (T * edge_i / edge in this order, in T's own precision: where the product is a whole number the truncation must see it)
         features = torch.cat([self.mult(rv.contiguous(), lv.contiguous(), T * float(rv.shape[2]) / edge) for rv, lv in pairs],
                              dim=1).contiguous()
-        params = mlp_parameters(self.filter)
+        params = None if graph else mlp_parameters(self.filter)
         if params is not None:
             W1, b1, W2, b2 = params
             B = features.shape[0]

@@ -31,6 +31,7 @@ SIGNATURES = {
     "dlpd_local_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "dlpd_local_max_poses": (_i, [_i, _i]),
     "dlpd_local_correlate": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _ll, _ll, _p]),
+    "dlpd_local_correlate_grad": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _ll, _ll, _p]),
     "dlpd_local_filter": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _i, _f, _f, _p, _p, _p, _p]),
     "dlpd_rotate_trilinear": (_i, [_p, _p, _p, _i, _i, _i, _ll, _f, _p]),
     "dlpd_zfft": (_i, [_p, _p, _p, _i, _i, _i, _ll, _i, _f, _p]),

@@ -1,7 +1,9 @@
 """``select_model(args)`` as the reference's test driver imports it (local_test.py:14, contract of
 /root/reference/src/local_train.py:19-43): the names in ``args.group`` / ``args.model`` /
-``args.filter`` pick a representation plugin and a filter, both moved to the GPU.  Training itself is
-out of scope of this build."""
+``args.filter`` pick a representation plugin and a filter, both moved to the GPU.
+What the reference's driver builds from them is here too: ``Models.LocalDockingModel`` (made differentiable by the trainer),
+``Models.BatchRankingLoss`` and ``Training.LocalTrainer`` (``optimize`` / ``score`` on ``(receptor_files, ligand_files,
+labels)``).  Its main loop and ``Dataset.get_dataset_stream`` are not: the stream still raises."""
 from Models import E3MultiResRepr4x4, SE3MultiResReprScalar, SimpleFilter, SyntheticRepr
 
 # equivariance group -> {model name -> constructor}

@@ -301,7 +301,20 @@ def local_correlate(receptor, ligand, T, R=None, radius=0, scale=1, coarse="floo
     ligand rotated by R_p (the 3x3 maps ``VolumeRotation`` samples with; None: as it is) -- the slices of
     MultiplyVolumes.multiply (MultiplyVolumes.py:13-47) summed directly.  receptor / ligand: (C, L, L, L) for all poses or
     (P, C, L, L, L); T (P, 3) int32 signed translations on the grid of ``scale`` * L points; coarse(t) = floor(t / scale)
-    ("floor": the global search's index) or trunc(t / scale) ("trunc": Python's int())."""
+    ("floor": the global search's index) or trunc(t / scale) ("trunc": Python's int()).
+    Differentiable with respect to ``receptor`` and ``ligand`` (first order; csrc/dlpd_local_grad.h): when autograd is enabled and
+    one of them requires a gradient the call is recorded, and the gradient of a volume shared by all poses is the sum over the
+    poses.  ``T`` and ``R`` receive no gradient, and the ligand's gradient THROUGH a rotation (``R`` given) is not built: that
+    combination raises.  In every other case the call is the plain forward."""
+    if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in (receptor, ligand)):
+        if R is not None and ligand.requires_grad:
+            raise RuntimeError("dlpd: local_correlate has no gradient with respect to a ROTATED ligand (R given): the scatter adjoint "
+                               "of the trilinear sample is not built -- rotate the coordinates, or detach the ligand")
+        return _LocalCorrelate.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib)
+    return _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib)
+
+
+def _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib):
     lib_ = lib or get_lib()
     T = T.contiguous()
     if T.dtype != torch.int32 or T.dim() != 2 or T.shape[1] != 3:
@@ -334,6 +347,53 @@ def local_correlate(receptor, ligand, T, R=None, radius=0, scale=1, coarse="floo
                   (_ptr(R) + 36 * beg) if R is not None else None, _ptr(T) + 12 * beg, _ptr(out) + 4 * C * W ** 3 * beg, _ptr(ws),
                   n, C, L, r, int(scale), COARSE_MODES[coarse], c0, rs, ls, st)
     return out
+
+
+class _LocalCorrelate(torch.autograd.Function):
+    """local_correlate under autograd: the forward is the plain call, the backward dlpd_local_correlate_grad for the gradients
+    that are needed.  Per-pose volumes go in batches of dlpd_local_max_poses, as in the forward; a volume shared by all poses
+    takes every pose in one call (its gradient's grid does not grow with P)."""
+
+    @staticmethod
+    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib):
+        ctx.save_for_backward(receptor, ligand, T, R)
+        ctx.args = (radius, scale, coarse, center, lib)
+        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R, radius, scale, coarse, center, lib)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gcorr):
+        receptor, ligand, T, R = ctx.saved_tensors
+        r, scale, coarse, center, lib = ctx.args
+        lib_ = lib or get_lib()
+        T = T.contiguous()
+        P = T.shape[0]
+        rec, rs = _pose_volumes(receptor.detach(), P, "receptor", lib)
+        lig, ls = _pose_volumes(ligand.detach(), P, "ligand", lib)
+        if R is not None:
+            R = _check(R, "R", lib)
+        g = _check(gcorr, "the gradient", lib)
+        C, L, W = rec.shape[-4], rec.shape[-1], 2 * r + 1
+        want_rec, want_lig = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        grec = torch.empty_like(rec) if want_rec else None
+        glig = torch.empty_like(lig) if want_lig else None
+        c0 = float(L) / 2.0 if center is None else float(center)
+        st = _stream(rec.device)
+        most = lib_.call("dlpd_local_max_poses", C, L)
+
+        def run(out_rec, out_lig, beg, n):
+            lib_.call("dlpd_local_correlate_grad", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg,
+                      (_ptr(R) + 36 * beg) if R is not None else None, _ptr(T) + 12 * beg, _ptr(g) + 4 * C * W ** 3 * beg,
+                      (_ptr(grec) + 4 * rs * beg) if out_rec else None, (_ptr(glig) + 4 * ls * beg) if out_lig else None,
+                      n, C, L, r, int(scale), COARSE_MODES[coarse], c0, rs, ls, st)
+        # a gradient per pose: batches of at most one launch's poses; a shared volume's gradient: all poses, one call
+        per_rec, per_lig = want_rec and rs != 0, want_lig and ls != 0
+        if per_rec or per_lig:
+            for beg in range(0, P, most):
+                run(per_rec, per_lig, beg, min(most, P - beg))
+        if (want_rec and rs == 0) or (want_lig and ls == 0):
+            run(want_rec and rs == 0, want_lig and ls == 0, 0, P)
+        return grec, glig, None, None, None, None, None, None, None
 
 
 def local_coarse_radius(radius, scale):
@@ -402,7 +462,8 @@ def local_filter(corr0, corr1, clash, T, radius, W1, b1, W2, b2, scale=1, coarse
 class MultiplyVolumes(nn.Module):
     """The reference's module (src/Models/MultiplyVolumes.py): ``forward(receptor (B, C, L, L, L), ligand (B, C, L, L, L),
     T (B, 3))`` -> (B, C), pair i at translation int(T[i]) (truncation toward zero), by the direct-correlation kernel.
-    Inference only; device tensors (``lib=``: the emulated library of the test-suite, host tensors)."""
+    Differentiable with respect to the two volumes, as ``local_correlate`` is (the adjoint kernel; first order only); T is
+    detached and truncated, it has no gradient.  Device tensors (``lib=``: the emulated library of the test-suite, host tensors)."""
 
     def __init__(self, lib=None):
         super().__init__()

@@ -225,6 +225,18 @@ int dlpd_local_max_poses(int C, int L);
 int dlpd_local_correlate(const float* rec, const float* lig, const float* R, const int* T, float* corr, void* ws, int P, int C,
                          int L, int r, int scale, int coarse_mode, float center, long long rec_pstride, long long lig_pstride,
                          void* stream);
+/* The adjoint of dlpd_local_correlate (training: src/Training/LocalTrainer.py:81-144 differentiates MultiplyVolumes):
+ *   grec[p,c,X] = sum_d gcorr[p,c,d] lig'_p[c, X - tau_p - d],  glig[p,c,x] = sum_d gcorr[p,c,d] rec[c, x + tau_p + d],
+ *   tau_p = coarse(T_p), d over the window, a term that leaves the box is 0.  rec, lig, R, T, the strides, scale, coarse_mode and
+ * center as the forward took them; gcorr (P, C, W^3).  grec / glig are laid out as rec / lig: (P, C, L^3) with that volume's
+ * per-pose stride, or, for stride 0 (one volume for all poses), (C, L^3) = the sum over the poses, added in pose order.  Either
+ * may be null (not wanted); both null is DLPD_ERR_ARG.  Every element is written (the caller need not clear them); no atomics
+ * and no workspace: the same bits run to run.  With R the sample of lig' is recomputed (no rotated volume is stored); glig
+ * with R -- the scatter adjoint of the trilinear gather -- is DLPD_ERR_UNSUPPORTED.  Limits as the forward; a gradient per
+ * pose takes at most dlpd_local_max_poses(C, L) poses per call. */
+int dlpd_local_correlate_grad(const float* rec, const float* lig, const float* R, const int* T, const float* gcorr, float* grec,
+                              float* glig, int P, int C, int L, int r, int scale, int coarse_mode, float center,
+                              long long rec_pstride, long long lig_pstride, void* stream);
 /* The filter of those poses (DockingModels.py:118-119; with clip / clash the search's DockingModels.py:74-83, Docker.py:226,232):
  * feat[d] = [clamp(corr0[:, d]), clamp(corr1[:, coarse(T_p + d) - coarse(T_p)])], score (P, W^3) = MLP(feat) * (clash < thr).
  * corr0 (P, C0, W^3) from dlpd_local_correlate(scale 1, r); corr1 (P, C1, Wc^3) from dlpd_local_correlate(scale, rc)
