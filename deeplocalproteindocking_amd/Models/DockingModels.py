@@ -17,7 +17,9 @@ import os
 import torch
 from torch import nn
 
-from deeplocalproteindocking_amd.ops import MultiplyVolumes, VolumeConvolution, VolumeRotation, filter_volumes, local_filter
+from deeplocalproteindocking_amd.ops import (MultiplyVolumes, VolumeConvolution, VolumeRotation, filter_volumes,
+                                             local_correlate_rotated, local_filter)
+from deeplocalproteindocking_amd.Utils.Conventions import rotation_pivot
 
 
 def init_weights(module):
@@ -132,7 +134,8 @@ class LocalDockingModel(nn.Module):
     is trained: under autograd the correlation goes through the differentiable ``MultiplyVolumes`` (the adjoint kernel of
     csrc/dlpd_local_grad.h), the representation runs as the plain torch modules it is made of, and the filter is CALLED -- the
     fused filter kernel has no graph and serves ``torch.no_grad()`` only, as before.
-    A filter that is not the reference's MLP (or is wider than the kernel's hidden widths) is called on the (B, sum C) features."""
+    A filter that is not the reference's MLP (or is wider than the kernel's hidden widths) is called on the (B, sum C) features.
+    ``forward_poses(receptor, ligand, R, T)`` scores P poses of ONE pair with one representation pass per protein (its docstring)."""
     FILES = GlobalDockingModel.FILES
 
     def __init__(self, representation, filter, lib=None, differentiable=False):
@@ -158,6 +161,34 @@ class LocalDockingModel(nn.Module):
         # (T * edge_i / edge in this order, in T's own precision: where the product is a whole number the truncation must see it)
         features = torch.cat([self.mult(rv.contiguous(), lv.contiguous(), T * float(rv.shape[2]) / edge) for rv, lv in pairs],
                              dim=1).contiguous()
+        return self._filter_features(features, graph)
+
+    def forward_poses(self, receptor, ligand, R, T, vol_rotate_center=None):
+        """ONE pair at P poses -- what a search's top list is: ``receptor`` / ``ligand`` (1, 11, L, L, L), ``R`` (P, 3, 3) the
+        maps ``VolumeRotation`` samples with, ``T`` (P, 3) on the input grid (scaled and truncated per resolution as ``forward``
+        does) -> (P, 1).  The representation runs ONCE per protein; per resolution the P rotated ligands are correlated with
+        the receptor by ``ops.local_correlate_rotated`` (no rotated volume in memory, differentiable in both volumes), where
+        the reference rotates the coordinates and pays one representation pass per pose.  ``vol_rotate_center``: the pivot on
+        the input grid (None: index L / 2), scaled to every resolution.  ``differentiable`` governs it as it governs ``forward``."""
+        graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if graph and not self.differentiable:
+            raise RuntimeError("dlpd: LocalDockingModel is inference only (no backward through the correlation kernel): "
+                               "call it under torch.no_grad(), or construct it with differentiable=True")
+        if receptor.shape[0] != 1 or ligand.shape[0] != 1 or R.dim() != 3 or T.shape[0] != R.shape[0]:
+            raise RuntimeError("dlpd: forward_poses expects one (1, C, L, L, L) pair, R (P, 3, 3) and T (P, 3)")
+        edge, P = receptor.shape[2], R.shape[0]
+        feats = []
+        for rv, lv in zip(self.representation(receptor), self.representation(ligand)):
+            Li = rv.shape[2]
+            Ti = (torch.as_tensor(T) * float(Li) / float(edge)).detach().trunc().to(torch.int32).to(rv.device)
+            Ri = R.detach().to(device=rv.device, dtype=torch.float32).contiguous()
+            corr = local_correlate_rotated(rv[0].contiguous(), lv[0].contiguous(), Ti, Ri, radius=0, scale=1, coarse="trunc",
+                                           center=rotation_pivot(vol_rotate_center, Li, edge), lib=self._lib)
+            feats.append(corr.reshape(P, -1))
+        return self._filter_features(torch.cat(feats, dim=1).contiguous(), graph)
+
+    def _filter_features(self, features, graph):
+        """(B, sum C) -> (B, 1): the fused filter kernel where there is no graph, the module otherwise."""
         params = None if graph else mlp_parameters(self.filter)
         if params is not None:
             W1, b1, W2, b2 = params

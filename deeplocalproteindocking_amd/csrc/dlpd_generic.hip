@@ -13,6 +13,7 @@
 #include "dlpd_internal.h"
 #include "dlpd_local.h"                 // local docking: direct correlation at given poses (any box size, no plan)
 #include "dlpd_local_grad.h"            // ... and its adjoint (the receptor's and the ligand's gradient)
+#include "dlpd_rotate_grad.h"           // ... and the adjoint of the rotation (the ligand's gradient through the poses)
 
 #define GEN_MAXN 256                      // box sizes up to 128 (tile: n_in x 64 complex <= 128 KB)
 

@@ -43,3 +43,13 @@ DLPD_D float trilinear_fetch(const float* __restrict__ v, int L, float px, float
   acc += v111 * (wx1 * wy1 * wz1);
   return acc;
 }
+
+// The weight trilinear_fetch gives the corner with index q (inside the box) along ONE axis for a sample at p -- the same
+// floorf and fraction; the sample's weight of voxel (qx, qy, qz) is wx * wy * wz, in that order.  For the adjoint of the
+// rotation (dlpd_rotate_grad.h).
+DLPD_D float trilinear_axis_weight(float p, int q) {
+  const float f = floorf(p);
+  const int i = (int)f;
+  const float a = p - f;
+  return i == q ? 1.f - a : (i + 1 == q ? a : 0.f);
+}

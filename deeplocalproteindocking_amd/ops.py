@@ -6,7 +6,11 @@ TorchProteinLibrary's volume ops, backed by libdlpd.so.
     VolumeConvolution(clip=None)(v1 (B,C,L,L,L), v2 same) -> (B,C,2L,2L,2L)
         reference calls: src/Docker/Docker.py:32,225 ; src/Models/DockingModels.py:48,71
 
-Inference only (the docking search runs under torch.no_grad(), local_test.py:67).
+    VolumeRotation also takes ONE (C,L,L,L) volume set for all B matrices, and is differentiable with respect to the
+    volume (csrc/dlpd_rotate_grad.h), as the local correlations below are (local_correlate, local_correlate_rotated,
+    MultiplyVolumes: csrc/dlpd_local_grad.h).  First order; R and T receive no gradient.
+
+Everything else is inference only (the docking search runs under torch.no_grad(), local_test.py:67).
 Box sizes 32 / 40 / 64 / 80 run the compiled FFT pipeline, any other box (<= 128) a plan-free slow path.
 Build-defined conventions (TPL source absent, parity unpinned): rotation about index L/2 with
 trilinear interpolation and zeros outside; ``clip`` clamps the correlation OUTPUT to +-clip.
@@ -40,17 +44,53 @@ class VolumeRotation(nn.Module):
         self.transpose = bool(transpose)
 
     def forward(self, volume, R):
+        """volume (B, C, L, L, L) with R (B, 3, 3), or ONE (C, L, L, L) volume set for all B matrices -> (B, C, L, L, L).
+        Differentiable with respect to ``volume`` (first order; csrc/dlpd_rotate_grad.h): when autograd is enabled and the
+        volume requires a gradient the call is recorded -- the shared form's gradient is the sum over the B rotations.  ``R``
+        receives no gradient.  In every other case the call is the plain forward (the same bits either way)."""
         volume, R = _check(volume, "volume", self.lib), _check(R, "R", self.lib)
-        B, C, L = volume.shape[0], volume.shape[1], volume.shape[2]
-        if R.shape[0] != B:
-            raise RuntimeError("dlpd: VolumeRotation batch mismatch: volume %d vs R %d" % (B, R.shape[0]))
-        out = torch.empty_like(volume)
+        if volume.dim() not in (4, 5):
+            raise RuntimeError("dlpd: VolumeRotation expects (B, C, L, L, L) or (C, L, L, L), got %s" % (tuple(volume.shape),))
+        L = volume.shape[-1]
+        if volume.dim() == 5 and R.shape[0] != volume.shape[0]:
+            raise RuntimeError("dlpd: VolumeRotation batch mismatch: volume %d vs R %d" % (volume.shape[0], R.shape[0]))
         c0 = float(L) / 2.0 if self.center is None else float(self.center)
         if self.scale is not None or self.axis_order != "xyz" or self.transpose:
             R = kernel_matrices(R, rotation_scale(self.scale, L), self.axis_order, self.transpose)
-        (self.lib or get_lib()).call("dlpd_rotate_trilinear", _ptr(volume), _ptr(R), _ptr(out), B, C, L, C * L ** 3, c0,
-                       _stream(volume.device))
-        return out
+        if torch.is_grad_enabled() and volume.requires_grad:
+            return _VolumeRotate.apply(volume, R, c0, self.lib)
+        return _volume_rotate_forward(volume, R, c0, self.lib)
+
+
+def _volume_rotate_forward(volume, M, c0, lib):
+    """M: the kernel's 3x3 maps (the conventions folded in)."""
+    B, C, L = M.shape[0], volume.shape[-4], volume.shape[-1]
+    out = torch.empty(B, C, L, L, L, dtype=torch.float32, device=volume.device)
+    (lib or get_lib()).call("dlpd_rotate_trilinear", _ptr(volume), _ptr(M), _ptr(out), B, C, L,
+                            C * L ** 3 if volume.dim() == 5 else 0, c0, _stream(volume.device))
+    return out
+
+
+class _VolumeRotate(torch.autograd.Function):
+    """VolumeRotation under autograd: the forward is the plain call, the backward dlpd_rotate_trilinear_grad with the same maps."""
+
+    @staticmethod
+    def forward(ctx, volume, M, c0, lib):
+        ctx.save_for_backward(M)
+        ctx.args = (tuple(volume.shape), c0, lib)
+        return _volume_rotate_forward(volume.detach(), M, c0, lib)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        (M,) = ctx.saved_tensors
+        shape, c0, lib = ctx.args
+        g = _check(gout, "the gradient", lib)
+        C, L = shape[-4], shape[-1]
+        gvol = torch.empty(shape, dtype=torch.float32, device=g.device)
+        (lib or get_lib()).call("dlpd_rotate_trilinear_grad", _ptr(g), _ptr(M), _ptr(gvol), M.shape[0], C, L,
+                                C * L ** 3 if len(shape) == 5 else 0, c0, 0, _stream(g.device))
+        return gvol, None, None, None
 
 
 class VolumeConvolution(nn.Module):
@@ -304,12 +344,13 @@ def local_correlate(receptor, ligand, T, R=None, radius=0, scale=1, coarse="floo
     ("floor": the global search's index) or trunc(t / scale) ("trunc": Python's int()).
     Differentiable with respect to ``receptor`` and ``ligand`` (first order; csrc/dlpd_local_grad.h): when autograd is enabled and
     one of them requires a gradient the call is recorded, and the gradient of a volume shared by all poses is the sum over the
-    poses.  ``T`` and ``R`` receive no gradient, and the ligand's gradient THROUGH a rotation (``R`` given) is not built: that
-    combination raises.  In every other case the call is the plain forward."""
+    poses.  ``T`` and ``R`` receive no gradient, and the ligand's gradient THROUGH a rotation (``R`` given) is not this
+    function's: that combination raises -- ``local_correlate_rotated`` is the call that has it.  In every other case the call
+    is the plain forward."""
     if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in (receptor, ligand)):
         if R is not None and ligand.requires_grad:
-            raise RuntimeError("dlpd: local_correlate has no gradient with respect to a ROTATED ligand (R given): the scatter adjoint "
-                               "of the trilinear sample is not built -- rotate the coordinates, or detach the ligand")
+            raise RuntimeError("dlpd: local_correlate has no gradient with respect to a ROTATED ligand (R given) -- call "
+                               "local_correlate_rotated, which has it, or detach the ligand")
         return _LocalCorrelate.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib)
     return _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib)
 
@@ -393,6 +434,72 @@ class _LocalCorrelate(torch.autograd.Function):
                 run(per_rec, per_lig, beg, min(most, P - beg))
         if (want_rec and rs == 0) or (want_lig and ls == 0):
             run(want_rec and rs == 0, want_lig and ls == 0, 0, P)
+        return grec, glig, None, None, None, None, None, None, None
+
+
+def local_correlate_rotated(receptor, ligand, T, R, radius=0, scale=1, coarse="floor", center=None, lib=None):
+    """``local_correlate(receptor, ligand, T, R=R, ...)`` -- the same call, the same bits, no rotated volume in memory --
+    differentiable in BOTH volumes: what trains a model on the poses of a search's top list (rotations of one ligand).
+    The receptor's gradient is the correlation's adjoint kernel with R (it recomputes the sample).  The ligand's goes in two
+    steps: the correlation's adjoint without R writes the gradient of every pose's ROTATED ligand into a workspace of at most
+    ``LOCAL_WS_BYTES`` (chunks of poses), and the rotation's adjoint (csrc/dlpd_rotate_grad.h) carries each chunk back through
+    its rotations -- summed over the poses, in pose order, for a ligand shared by all of them.  First order; ``T`` and ``R``
+    receive no gradient."""
+    if R is None:
+        raise RuntimeError("dlpd: local_correlate_rotated needs the rotations R (without them: local_correlate)")
+    if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in (receptor, ligand)):
+        return _LocalCorrelateRotated.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib)
+    return _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib)
+
+
+class _LocalCorrelateRotated(torch.autograd.Function):
+    """local_correlate_rotated under autograd (its docstring).  Batching as _LocalCorrelate; the ligand's chunks are bounded by
+    the workspace and by dlpd_local_max_poses, and from the second chunk on a shared ligand's sums start at the stored values
+    (``accumulate``): the chunked result has the bits of the unsplit one."""
+
+    @staticmethod
+    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib):
+        ctx.save_for_backward(receptor, ligand, T, R)
+        ctx.args = (radius, scale, coarse, center, lib)
+        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R, radius, scale, coarse, center, lib)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gcorr):
+        receptor, ligand, T, R = ctx.saved_tensors
+        r, scale, coarse, center, lib = ctx.args
+        lib_ = lib or get_lib()
+        T = T.contiguous()
+        P = T.shape[0]
+        rec, rs = _pose_volumes(receptor.detach(), P, "receptor", lib)
+        lig, ls = _pose_volumes(ligand.detach(), P, "ligand", lib)
+        R = _check(R, "R", lib)
+        g = _check(gcorr, "the gradient", lib)
+        C, L, W = rec.shape[-4], rec.shape[-1], 2 * r + 1
+        vol = C * L ** 3
+        want_rec, want_lig = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        grec = torch.empty_like(rec) if want_rec else None
+        glig = torch.empty_like(lig) if want_lig else None
+        c0 = float(L) / 2.0 if center is None else float(center)
+        st = _stream(rec.device)
+        most = lib_.call("dlpd_local_max_poses", C, L)
+
+        def run(Rp, out_rec, out_lig, lig_stride, beg, n):
+            lib_.call("dlpd_local_correlate_grad", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg, Rp, _ptr(T) + 12 * beg,
+                      _ptr(g) + 4 * C * W ** 3 * beg, out_rec, out_lig, n, C, L, r, int(scale), COARSE_MODES[coarse], c0, rs,
+                      lig_stride, st)
+        if want_rec:
+            step = most if rs != 0 else P             # a gradient per pose: one launch's poses; a shared receptor: all in one call
+            for beg in range(0, P, step):
+                run(_ptr(R) + 36 * beg, _ptr(grec) + 4 * rs * beg, None, ls, beg, min(step, P - beg))
+        if want_lig:
+            chunk = max(1, min(P, LOCAL_WS_BYTES // (4 * vol), most))
+            ws = torch.empty(chunk * vol, dtype=torch.float32, device=rec.device)
+            for beg in range(0, P, chunk):
+                n = min(chunk, P - beg)
+                run(None, None, _ptr(ws), vol, beg, n)             # the gradient of each pose's rotated ligand (no ligand is read)
+                lib_.call("dlpd_rotate_trilinear_grad", _ptr(ws), _ptr(R) + 36 * beg, _ptr(glig) + 4 * ls * beg, n, C, L, ls, c0,
+                          1 if (ls == 0 and beg > 0) else 0, st)
         return grec, glig, None, None, None, None, None, None, None
 
 

@@ -65,6 +65,17 @@ int dlpd_fused_hidden_pad(int H, int L, int two_res);
  * vol (B,C,L^3) with batch stride vol_bstride floats (0: one volume set shared by all b). */
 int dlpd_rotate_trilinear(const float* vol, const float* R, float* out, int B, int C, int L,
                           long long vol_bstride, float center, void* stream);
+/* The adjoint of that call (TPL's VolumeRotation is a differentiable operator; src/Docker/Docker.py:218 is the call a model
+ * trained on a search's top list differentiates): gout (B,C,L^3) the gradient of `out`, R and center as the forward took them,
+ *   gvol[b,c](q) = sum_i w_b(i, q) gout[b,c](i),  w_b(i, q) the trilinear weight the forward's sample of output voxel i gives
+ *   source voxel q (corners outside the box carry none).
+ * gvol is laid out as vol was: (B,C,L^3) with batch stride gvol_bstride floats, or, for stride 0 (one volume set shared by all
+ * b), (C,L^3) = the sum over b, added in the order of b.  accumulate != 0: the sums start at the values gvol holds (B split
+ * over several calls gives the bits of one call) instead of 0.  A gather over the output voxels that can reach q -- exact for
+ * any invertible 3x3 map --: no atomics, no workspace, every element written once, the same bits run to run.
+ * Null pointers, B or C <= 0 or a negative stride: DLPD_ERR_ARG; L < 2 or L > 128: DLPD_ERR_UNSUPPORTED. */
+int dlpd_rotate_trilinear_grad(const float* gout, const float* R, float* gvol, int B, int C, int L, long long gvol_bstride,
+                               float center, int accumulate, void* stream);
 
 /* Stage K1 of TPL VolumeConvolution (src/Models/DockingModels.py:71, src/Docker/Docker.py:225),
  * optionally fused with the rotation of Docker.py:218: z-axis R2C of (rotated) volumes.

@@ -1,0 +1,217 @@
+"""Time the adjoint of the trilinear volume rotation (csrc/dlpd_rotate_grad.h) at the reference's shapes [16 @ 80^3, 32 @ 40^3]
+for 64 poses of ONE shared ligand, beside the forward kernel (k_rotate) on the same shapes and the backward of torch's
+affine_grid + grid_sample (trilinear, zeros) into its input -- what a user would otherwise write -- and one
+LocalDockingModel.forward_poses step (forward + backward).  Prints one JSON line per part.
+
+    python scripts/bench_rotate_grad.py [--poses 64] [--repeats 30]          # device-event timing
+    python scripts/bench_rotate_grad.py --profile prof/rotate_grad           # + the kernels alone: a child process under
+                                                                             #   rocprofv3 --kernel-trace --stats
+    python scripts/bench_rotate_grad.py --counters prof/rotate_grad_pmc      # + hardware counters of the adjoint kernel, in
+                                                                             #   a run of their own (no tracing beside them)
+    python scripts/bench_rotate_grad.py --kernel-only | --step-only          # what those children run
+
+The adjoint's floor is memory traffic: it reads B C L^3 4 bytes (the gradient of every rotated copy) and writes C L^3 4.
+Needs a GPU: no CPU fallback."""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+import __graft_entry__ as entry
+
+SHAPES = ((16, 80), (32, 40))
+STEPS = 10
+
+
+def _timed(fn, repeats, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
+
+
+def rotations(P, seed=3):
+    """P proper rotations (QR of a normal matrix, the sign fixed), float32 (P, 3, 3)."""
+    q, r = np.linalg.qr(np.random.RandomState(seed).randn(P, 3, 3))
+    q = q * np.sign(np.diagonal(r, axis1=1, axis2=2))[:, None, :]
+    q[:, :, 0] *= np.linalg.det(q)[:, None]
+    return torch.from_numpy(q).float().contiguous()
+
+
+def floor_bytes(P, C, L):
+    return (P + 1) * C * L ** 3 * 4
+
+
+def kernels(lib, dev, P):
+    """Per shape: closures that launch the adjoint (stride 0: the sum over the poses) and the forward (one shared volume)."""
+    from deeplocalproteindocking_amd.engine import _stream
+    out = []
+    R = rotations(P).to(dev)
+    g_ = torch.Generator().manual_seed(5)
+    for C, L in SHAPES:
+        vol = torch.randn(C, L, L, L, generator=g_).to(dev)
+        gout = torch.randn(P, C, L, L, L, generator=g_).to(dev)
+        gvol, rot = torch.empty_like(vol), torch.empty_like(gout)
+        st, c0 = _stream(dev), L / 2.0
+
+        def adj(gout=gout, gvol=gvol, C=C, L=L, c0=c0):
+            lib.call("dlpd_rotate_trilinear_grad", gout.data_ptr(), R.data_ptr(), gvol.data_ptr(), P, C, L, 0, c0, 0, st)
+
+        def fwd(vol=vol, rot=rot, C=C, L=L, c0=c0):
+            lib.call("dlpd_rotate_trilinear", vol.data_ptr(), R.data_ptr(), rot.data_ptr(), P, C, L, 0, c0, st)
+        out.append((C, L, adj, fwd, vol, gout, R))
+    return out
+
+
+def torch_backward(vol, gout, R):
+    """The backward of affine_grid + grid_sample into ONE shared input (expanded over the poses): autograd's scatter with
+    float atomics, then the sum over the poses."""
+    P = R.shape[0]
+    v = vol.detach().clone().requires_grad_()
+    theta = torch.cat([R.flip(1).flip(2), torch.zeros(P, 3, 1, device=R.device)], dim=2)
+    grid = torch.nn.functional.affine_grid(theta, (P,) + tuple(vol.shape), align_corners=True)
+    out = torch.nn.functional.grid_sample(v[None].expand(P, -1, -1, -1, -1), grid, mode="bilinear", padding_mode="zeros",
+                                          align_corners=True)
+    return lambda: torch.autograd.grad(out, v, gout, retain_graph=True)
+
+
+def model_step(dev, P):
+    from deeplocalproteindocking_amd.Models import E3MultiResRepr4x4, LocalDockingModel, SimpleFilter
+    torch.manual_seed(1)
+    net = E3MultiResRepr4x4()
+    model = LocalDockingModel(net, SimpleFilter(net.get_num_outputs()), differentiable=True).to(dev).train()
+    g_ = torch.Generator().manual_seed(2)
+    L = SHAPES[0][1]
+    rec, lig = torch.rand(1, 11, L, L, L, generator=g_).to(dev), torch.rand(1, 11, L, L, L, generator=g_).to(dev)
+    R = rotations(P).to(dev)
+    T = torch.from_numpy(np.random.RandomState(8).randint(-20, 21, size=(P, 3))).float().to(dev)
+
+    def step():
+        model.zero_grad()
+        model.forward_poses(rec, lig, R, T).sum().backward()
+    return step
+
+
+def _stats(directory):
+    files = glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True)
+    assert files, "rocprofv3 wrote no kernel statistics under %s" % directory
+    return list(csv.DictReader(open(files[0])))
+
+
+def _ms(rows, *needles):
+    return sum(float(r["TotalDurationNs"]) for r in rows if any(n in r["Name"] for n in needles)) / 1e6 / STEPS
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--poses", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=30)
+    ap.add_argument("--profile", default=None, help="directory for the rocprofv3 kernel traces")
+    ap.add_argument("--counters", default=None, help="directory for the counter run of the adjoint kernel")
+    ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--adjoint-only", action="store_true")
+    ap.add_argument("--step-only", action="store_true")
+    ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--variants", default="", help="name=library,... : A/B builds of the adjoint kernel (scripts/build_variant.py "
+                    "NAME --generic=-DDLPD_ROT_GRAD_CC=8 | -DDLPD_ROT_GRAD_SKIP=0), timed beside the product library")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_rotate_grad.py needs a GPU"
+    entry.build()
+    from deeplocalproteindocking_amd._lib import get_lib
+    lib, dev, P = get_lib(), torch.device("cuda:0"), args.poses
+    if args.step_only:
+        step = model_step(dev, P)
+        for _ in range(2 + STEPS):
+            step()
+        torch.cuda.synchronize()
+        return
+    ks = kernels(lib, dev, P)
+    if args.kernel_only or args.adjoint_only:
+        for _ in range(STEPS):
+            for _, _, adj, fwd, _, _, _ in ks:
+                adj()
+                if not args.adjoint_only:
+                    fwd()
+        torch.cuda.synchronize()
+        return
+    for C, L, adj, fwd, vol, gout, R in ks:
+        row = {"part": "rotation %d @ %d^3, %d poses of one volume (device events)" % (C, L, P), "adjoint_ms": _timed(adj, args.repeats),
+               "forward_ms": _timed(fwd, args.repeats), "torch_grid_sample_backward_ms": _timed(torch_backward(vol, gout, R), args.repeats),
+               "adjoint_floor_bytes": floor_bytes(P, C, L)}
+        row["adjoint_over_torch"] = row["adjoint_ms"]["median"] / row["torch_grid_sample_backward_ms"]["median"]
+        row["adjoint_achieved_TB_per_s"] = row["adjoint_floor_bytes"] / (row["adjoint_ms"]["median"] * 1e-3) / 1e12
+        print(json.dumps(row), flush=True)
+    if args.variants:
+        from deeplocalproteindocking_amd._lib import DlpdLib
+        libs = [("product", lib)] + [(nv.split("=")[0], DlpdLib(nv.split("=")[1])) for nv in args.variants.split(",")]
+        sets = [(name, kernels(l, dev, P)) for name, l in libs]
+        for i, (C, L) in enumerate(SHAPES):
+            row = {"part": "adjoint variants %d @ %d^3, %d poses (device events, alternating)" % (C, L, P)}
+            for rnd in range(2):                                  # every variant twice, alternating: the spread between rounds
+                for name, k in sets:
+                    row["%s_ms_round%d" % (name, rnd)] = _timed(k[i][2], args.repeats)["median"]
+            print(json.dumps(row), flush=True)
+        del sets, libs
+    del ks
+    torch.cuda.empty_cache()
+    if not args.skip_step:
+        print(json.dumps({"part": "forward_poses step, 11 @ %d^3, %d poses (device events)" % (SHAPES[0][1], P),
+                          "step_ms": _timed(model_step(dev, P), max(5, args.repeats // 3), warmup=2)}), flush=True)
+    me = [sys.executable, os.path.abspath(__file__), "--poses", str(P)]
+    if args.profile:
+        for name, flag in (("kernels", "--kernel-only"), ("step", "--step-only")):
+            if name == "step" and args.skip_step:
+                continue
+            d = os.path.join(args.profile, name)
+            os.makedirs(d, exist_ok=True)
+            subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + me + [flag],
+                           check=True, timeout=900, stdout=subprocess.DEVNULL)
+            rows = _stats(d)
+            if name == "kernels":
+                adj_ms, fwd_ms = _ms(rows, "k_rotate_adjoint"), _ms(rows, "k_rotate(")
+                fl = sum(floor_bytes(P, C, L) for C, L in SHAPES)
+                print(json.dumps({"part": "kernels alone, both shapes (rocprofv3 --kernel-trace --stats)", "launches": STEPS,
+                                  "adjoint_ms": adj_ms, "forward_ms": fwd_ms, "adjoint_floor_bytes": fl,
+                                  "adjoint_achieved_TB_per_s": fl / (adj_ms * 1e-3) / 1e12}), flush=True)
+            else:
+                n = (2 + STEPS) / float(STEPS)                    # (the child's two warm-up steps are in the trace)
+                total = sum(float(r["TotalDurationNs"]) for r in rows) / 1e6 / STEPS
+                adj_ms, corr_ms = _ms(rows, "k_rotate_adjoint"), _ms(rows, "k_local_corr", "k_local_reduce")
+                print(json.dumps({"part": "forward_poses step by kernel (rocprofv3 --kernel-trace --stats)", "steps": 2 + STEPS,
+                                  "rotation_adjoint_ms_per_step": adj_ms / n, "correlation_ms_per_step": corr_ms / n,
+                                  "representation_and_rest_ms_per_step": (total - adj_ms - corr_ms) / n,
+                                  "kernel_time_ms_per_step": total / n}), flush=True)
+    if args.counters:
+        os.makedirs(args.counters, exist_ok=True)
+        subprocess.run(["rocprofv3", "--pmc", "SQ_WAVES", "SQ_INSTS_VALU", "SQ_INSTS_VMEM_RD", "SQ_WAIT_INST_ANY", "SQ_BUSY_CYCLES",
+                        "--output-format", "csv", "-d", args.counters, "--"] + me + ["--adjoint-only"],
+                       check=True, timeout=900, stdout=subprocess.DEVNULL)
+        files = glob.glob(os.path.join(args.counters, "**", "*counter_collection.csv"), recursive=True)
+        assert files, "rocprofv3 wrote no counters under %s" % args.counters
+        sums = {}
+        for r in csv.DictReader(open(files[0])):
+            if "k_rotate_adjoint" in r.get("Kernel_Name", ""):
+                key = (r.get("Grid_Size", "?"), r["Counter_Name"])
+                sums[key] = sums.get(key, 0.0) + float(r["Counter_Value"])
+        print(json.dumps({"part": "adjoint kernel counters, summed over %d launches (rocprofv3 --pmc, a run of its own)" % STEPS,
+                          "counters": {"grid %s %s" % k: v for k, v in sorted(sums.items())}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
