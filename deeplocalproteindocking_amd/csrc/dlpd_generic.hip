@@ -16,6 +16,7 @@
 #include "dlpd_rotate_grad.h"           // ... and the adjoint of the rotation (the ligand's gradient through the poses)
 
 #define GEN_MAXN 256                      // box sizes up to 128 (tile: n_in x 64 complex <= 128 KB)
+#define GEN_NACC 4                        // partial sums per output of a direct transform (the final adds are written for 4)
 
 // transform along a MIDDLE axis: in (outer, n_in, inner) -> out (outer, N, inner), inner contiguous;
 // out[o][k][i] = sum_j in[o][j][i] exp(dir 2 pi i j k / N).  grid (ceil(inner / 64), outer), block 256 = 64 columns x 4
@@ -41,25 +42,37 @@ __global__ void __launch_bounds__(256) k_gdft_mid(const cplx* __restrict__ in, c
   if (i0 + c >= inner) return;
   cplx* dst = out + (size_t)o * N * inner + i0 + c;
   for (int k0 = 4 * g; k0 < N; k0 += 16) {
-    float ar[4] = {0.f, 0.f, 0.f, 0.f}, ai[4] = {0.f, 0.f, 0.f, 0.f};
-    int idx[4] = {0, 0, 0, 0};
-    for (int j = 0; j < n_in; j++) {
-      const cplx v = tile[j * 64 + c];
+    // GEN_NACC partial sums per output, term j into sum j mod GEN_NACC, added pairwise at the end: where the terms are in
+    // phase (the peak of an impulse's correlation) a single running sum grows like j and its rounding error like n^1.5 eps;
+    // split, each sum is a quarter as long and the error of the total a quarter as large (half, for terms of random phase)
+    float ar[GEN_NACC][4], ai[GEN_NACC][4];
 #pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const cplx w = tw[idx[u]];
-        ar[u] = fmaf(v.x, w.x, fmaf(-v.y, w.y, ar[u]));
-        ai[u] = fmaf(v.x, w.y, fmaf(v.y, w.x, ai[u]));
-        // (j k) mod N, incrementally.  The step is reduced mod N first: for an odd box N = 2L is not a multiple of 4
-        // and the lanes k0 + u >= N of the last round (their results are discarded below) would otherwise walk idx past
-        // the table -- a read beyond the LDS allocation (harmless zeros on the GPU, a heap over-read in the emulator)
-        idx[u] += (k0 + u < N) ? (k0 + u) : (k0 + u - N);
-        if (idx[u] >= N) idx[u] -= N;
+    for (int a = 0; a < GEN_NACC; a++)
+#pragma unroll
+      for (int u = 0; u < 4; u++) ar[a][u] = ai[a][u] = 0.f;
+    int idx[4] = {0, 0, 0, 0};
+    for (int j0 = 0; j0 < n_in; j0 += GEN_NACC) {
+#pragma unroll
+      for (int a = 0; a < GEN_NACC; a++) {
+        if (j0 + a >= n_in) break;
+        const cplx v = tile[(j0 + a) * 64 + c];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const cplx w = tw[idx[u]];
+          ar[a][u] = fmaf(v.x, w.x, fmaf(-v.y, w.y, ar[a][u]));
+          ai[a][u] = fmaf(v.x, w.y, fmaf(v.y, w.x, ai[a][u]));
+          // (j k) mod N, incrementally.  The step is reduced mod N first: for an odd box N = 2L is not a multiple of 4
+          // and the lanes k0 + u >= N of the last round (their results are discarded below) would otherwise walk idx past
+          // the table -- a read beyond the LDS allocation (harmless zeros on the GPU, a heap over-read in the emulator)
+          idx[u] += (k0 + u < N) ? (k0 + u) : (k0 + u - N);
+          if (idx[u] >= N) idx[u] -= N;
+        }
       }
     }
 #pragma unroll
     for (int u = 0; u < 4; u++)
-      if (k0 + u < N) dst[(size_t)(k0 + u) * inner] = c_make(ar[u], ai[u]);
+      if (k0 + u < N)
+        dst[(size_t)(k0 + u) * inner] = c_make((ar[0][u] + ar[1][u]) + (ar[2][u] + ar[3][u]), (ai[0][u] + ai[1][u]) + (ai[2][u] + ai[3][u]));
   }
 }
 
@@ -91,15 +104,22 @@ __global__ void __launch_bounds__(256) k_gdft_last(const void* __restrict__ in, 
   __syncthreads();
   if (p0 + p >= P) return;
   for (int k = kl; k < N; k += 16) {
-    float ar = 0.f, ai = 0.f;
+    float pr[GEN_NACC], pi[GEN_NACC];              // partial sums, as in k_gdft_mid
+#pragma unroll
+    for (int a = 0; a < GEN_NACC; a++) pr[a] = pi[a] = 0.f;
     int idx = 0;
-    for (int j = 0; j < n_in; j++) {
-      const cplx v = tile[p * RSL + j], w = tw[idx];
-      ar = fmaf(v.x, w.x, fmaf(-v.y, w.y, ar));
-      ai = fmaf(v.x, w.y, fmaf(v.y, w.x, ai));
-      idx += k;
-      if (idx >= N) idx -= N;
+    for (int j0 = 0; j0 < n_in; j0 += GEN_NACC) {
+#pragma unroll
+      for (int a = 0; a < GEN_NACC; a++) {
+        if (j0 + a >= n_in) break;
+        const cplx v = tile[p * RSL + j0 + a], w = tw[idx];
+        pr[a] = fmaf(v.x, w.x, fmaf(-v.y, w.y, pr[a]));
+        pi[a] = fmaf(v.x, w.y, fmaf(v.y, w.x, pi[a]));
+        idx += k;
+        if (idx >= N) idx -= N;
+      }
     }
+    const float ar = (pr[0] + pr[1]) + (pr[2] + pr[3]), ai = (pi[0] + pi[1]) + (pi[2] + pi[3]);
     if (out_real) {
       float r = ar * scale;
       if (has_clip) r = DLPD_CLAMP(r, clip);

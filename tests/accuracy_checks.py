@@ -543,8 +543,9 @@ def check_unequal_scales(lib, device, L, C, probed, seed=0):
 # section 4: stand-alone operators and the local path
 # ----------------------------------------------------------------------------------------------------------------------
 
-def check_volume_convolution(lib, device, L, C=2, embed=True, seed=0):
-    """ops.VolumeConvolution on dense, impulse, impulse x impulse, spectrally extreme and face-mass inputs.
+def check_volume_convolution(lib, device, L, C=2, embed=True, seed=0, inputs=None):
+    """ops.VolumeConvolution on dense, impulse, impulse x impulse, spectrally extreme and face-mass inputs (``inputs``: the
+    names of those to run, None: all five -- the largest boxes take three, the float64 transform on the host is what costs).
 
     The plan-free route (boxes without a compiled plan, embed=False) answers to a wider bound, by its formulation: every
     1-D transform there is a DIRECT sum (csrc/dlpd_generic.hip: O(n N), no radix plan) of n = L terms on the way in and
@@ -553,7 +554,10 @@ def check_volume_convolution(lib, device, L, C=2, embed=True, seed=0):
     (one rounding per pass; Gentleman and Sande 1966): a direct transform may be sqrt(N / log2 N) further from the truth than
     the oracle's FFT -- 3.45 at box 37, 2.15 at box 10 -- and both margins are multiplied by exactly that.  (Measured on an
     MI355X at box 37: 1.6 RMS on dense input, 2.6 on impulse x impulse, whose error is all transform and no input; the
-    oracle's own transform of length 74 = 2 x 37 holds a direct 37-point butterfly, so the full factor is not reached.)"""
+    oracle's own transform of length 74 = 2 x 37 holds a direct 37-point butterfly, so the full factor is not reached.)
+    Those figures are of a single running sum per output.  At box 128 that missed the bound on impulse x impulse (11.49 RMS,
+    19.58 max against 11.31 / 16.97): at the peak all 256 terms are in phase and the error of a running sum grows like
+    n^1.5 eps, not like the random walk above.  The kernels now keep four partial sums per output (GEN_NACC)."""
     from deeplocalproteindocking_amd.ops import VolumeConvolution
     g = torch.Generator().manual_seed(seed)
     rec = torch.randn(C, L, L, L, generator=g)
@@ -561,12 +565,15 @@ def check_volume_convolution(lib, device, L, C=2, embed=True, seed=0):
     imp2, where2 = impulses(C, L, 4)
     route = "compiled" if lib_supports(lib, L) else ("embedded" if embed else "plan-free")
     conv = VolumeConvolution(clip=None, lib=lib, embed=embed)
-    inputs = [("dense", rec, torch.randn(C, L, L, L, generator=g), None),
-              ("impulse ligand", rec, imp, torch.stack([shifted(rec[c], where[c]) for c in range(C)])),
-              ("impulse x impulse", imp2, imp, None),
-              ("extreme spectra", rec, extreme_ligands(C, L, seed + 1) * 10, None),
-              ("mass on the faces", rec, face_mass(C, L, seed + 2), None)]
-    for name, v1, v2, exact in inputs:
+    cases = [("dense", rec, torch.randn(C, L, L, L, generator=g), None),
+             ("impulse ligand", rec, imp, torch.stack([shifted(rec[c], where[c]) for c in range(C)])),
+             ("impulse x impulse", imp2, imp, None),
+             ("extreme spectra", rec, extreme_ligands(C, L, seed + 1) * 10, None),
+             ("mass on the faces", rec, face_mass(C, L, seed + 2), None)]
+    assert inputs is None or set(inputs) <= {c[0] for c in cases}, inputs
+    for name, v1, v2, exact in cases:
+        if inputs is not None and name not in inputs:
+            continue
         out = conv(v1[None].to(device), v2[None].to(device)).cpu()[0]
         x64 = orc.correlate_fft(v1[None], v2[None], dtype=torch.float64)[0]
         if exact is not None:
@@ -577,8 +584,53 @@ def check_volume_convolution(lib, device, L, C=2, embed=True, seed=0):
             x64 = torch.zeros_like(x64)
             for c in range(C):
                 x64[(c,) + tuple((where2[c][a] - where[c][a]) % N for a in range(3))] = 1.0
-        growth = float(np.sqrt(2 * L / np.log2(2 * L))) if route == "plan-free" else 1.0
+        growth = plan_free_growth(L) if route == "plan-free" else 1.0
         yardstick("VolumeConvolution box %d (%s), %s" % (L, route, name), out, orc.correlate_fft(v1[None], v2[None])[0], x64, growth=growth)
+
+
+def plan_free_growth(L):
+    """The formulation factor of the plan-free route at box L (derived in check_volume_convolution)."""
+    return float(np.sqrt(2 * L / np.log2(2 * L)))
+
+
+def check_plan_free_chunks(lib, device, L=128, C=12, seed=0):
+    """ops._vc_generic keeps its scratch under 4 GB by taking the volumes in chunks: C volumes at a box where they exceed one
+    chunk (asserted from the library's own workspace size).  The last channel is a copy of the first on both sides and lies
+    behind the chunk boundary: its output must have the first's bytes (a chunk that read or wrote at the wrong volume
+    offset cannot), and the first answers to float64 by the plan-free yardstick -- one transform on the host, not C."""
+    from deeplocalproteindocking_amd._lib import get_lib
+    from deeplocalproteindocking_amd.ops import VolumeConvolution
+    per = (lib or get_lib()).call("dlpd_correlate_generic_ws_bytes", 1, int(L))
+    assert C > (4 << 30) // per >= 1, ("the chunk loop must iterate twice", per, C)
+    chunk = min((4 << 30) // per, 65535 // (2 * L))
+    g = torch.Generator().manual_seed(seed)
+    v1, v2 = torch.randn(1, C, L, L, L, generator=g), torch.randn(1, C, L, L, L, generator=g)
+    v1[0, C - 1], v2[0, C - 1] = v1[0, 0], v2[0, 0]
+    out = VolumeConvolution(clip=None, lib=lib, embed=False)(v1.to(device), v2.to(device))
+    first, last, others = out[0, 0].cpu(), out[0, C - 1].cpu(), out[0, 1:C - 1].abs().amax(dim=(1, 2, 3)).cpu()
+    del out
+    assert first.numpy().tobytes() == last.numpy().tobytes(), "the volume behind the chunk boundary"
+    assert bool((others > 0).all()) and bool(torch.isfinite(others).all())
+    x64 = orc.correlate_fft(v1[:, :1], v2[:, :1], dtype=torch.float64)[0, 0]
+    return yardstick("VolumeConvolution box %d (plan-free), %d volumes in chunks of %d, volume 0" % (L, C, chunk), first,
+                     orc.correlate_fft(v1[:, :1], v2[:, :1])[0, 0], x64, growth=plan_free_growth(L))
+
+
+def check_plan_free_clamp(lib, device, L=84, C=2, seed=0):
+    """The clamp of the plan-free route is the last operation of its last kernel: with ``clip`` at the median of the
+    unclipped |output| the clipped call equals torch.clamp of the unclipped one bit for bit, and about half the elements
+    change."""
+    from deeplocalproteindocking_amd.ops import VolumeConvolution
+    g = torch.Generator().manual_seed(seed)
+    v1, v2 = torch.randn(1, C, L, L, L, generator=g).to(device), torch.randn(1, C, L, L, L, generator=g).to(device)
+    assert not lib_supports(lib, L)
+    plain = VolumeConvolution(clip=None, lib=lib, embed=False)(v1, v2).cpu()
+    clip = float(plain.abs().reshape(-1).median())
+    clipped = VolumeConvolution(clip=clip, lib=lib, embed=False)(v1, v2).cpu()
+    changed = float((clipped != plain).float().mean())
+    print("ACCURACY | VolumeConvolution box %d (plan-free), clip %.4g: %.3f of the elements clamped" % (L, clip, changed), flush=True)
+    assert clip > 0 and 0.3 <= changed <= 0.7, changed
+    assert torch.equal(clipped, torch.clamp(plain, -clip, clip))
 
 
 def lib_supports(lib, L):

@@ -130,6 +130,11 @@ def test_volume_convolution(emu, L, embed):
     acc.check_volume_convolution(emu, CPU, L, C=2 if L > 10 else 3, embed=embed, seed=30 + L)
 
 
+def test_volume_convolution_plan_free_clamp_bites(emu):
+    """The body of the device's check at box 84, on the emulator at box 10."""
+    acc.check_plan_free_clamp(emu, CPU, 10, 2, seed=32)
+
+
 @pytest.mark.parametrize("L", [10, 32])
 def test_volume_rotation(emu, L):
     acc.check_volume_rotation(emu, CPU, L, C=2, seed=40 + L)

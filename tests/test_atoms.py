@@ -407,8 +407,11 @@ def _volume_case(seed, C=4, L=32):
     g = torch.Generator().manual_seed(seed)
     rec, lig = torch.randn(1, C, L, L, L, generator=g) * 0.1, torch.randn(1, C, L, L, L, generator=g) * 0.1
     recf, ligf = torch.rand(L, L, L, generator=g), torch.rand(L, L, L, generator=g)
-    R = orc.euler_to_matrix([0.3, -1.0, 2.0], [1.1, 0.4, 2.2], [-2.0, 2.5, 0.1])
-    return rec, lig, recf, ligf, R
+    return rec, lig, recf, ligf, _three_rotations()
+
+
+def _three_rotations():
+    return orc.euler_to_matrix([0.3, -1.0, 2.0], [1.1, 0.4, 2.2], [-2.0, 2.5, 0.1])
 
 
 def _check_lists(got, want, scale, K):
@@ -586,6 +589,82 @@ def test_uncompiled_box_sizes_take_the_generic_path_on_gpu():
     entry.build()
     _run_uncompiled_box(None, torch.device("cuda:0"), 48, 200)
     _run_uncompiled_box(None, torch.device("cuda:0"), 50, 200)
+
+
+def _near_entries(want, band):
+    """How many entries of a ranked list have another entry of the list within ``band`` of their score."""
+    s = np.array([w[4] for w in want], dtype=np.float64)
+    d = np.abs(s[:, None] - s[None, :])
+    np.fill_diagonal(d, np.inf)
+    return int((d.min(axis=1) <= band).sum())
+
+
+def _run_box_above_80(lib, device, L, sizes, nrot, K, biting_clip=False):
+    """Boxes 81 .. 128 have no compiled plan and no compiled box to sit in: the stand-alone ops -- grid-stride rotation,
+    plan-free correlation (csrc/dlpd_generic.hip, 87 - 130 KB of LDS per block), dlpd_filter_mask at N = 168 .. 256, device
+    top-K over N^3 candidates -- are the default path and the only one.  Ranked list against the oracle's.
+
+    Inputs (not _volume_case: at amplitude 0.1 the correlations of boxes this size exceed the clip of 5 and the oracle's whole
+    list collapses to one tied score): randn * sqrt(1.5 / l^1.5) per grid of edge l, which keeps the correlations of order 1;
+    rand clash volumes; the threshold at the median of the float64 clash correlation of the first rotation.
+    biting_clip: the model's clip at the 0.9 quantile of the oracle's |correlation| of the first rotation."""
+    from deeplocalproteindocking_amd.Docker import Docker
+    from deeplocalproteindocking_amd.Models import GlobalDockingModel, SimpleFilter, SyntheticRepr
+    g = torch.Generator().manual_seed(100 + L)
+    rec, lig = [], []
+    for i, c in enumerate(sizes):
+        l = L >> i
+        amp = float(np.sqrt(1.5 / l ** 1.5))
+        rec.append(torch.randn(1, c, l, l, l, generator=g) * amp)
+        lig.append(torch.randn(1, c, l, l, l, generator=g) * amp)
+    recf, ligf = torch.rand(L, L, L, generator=g), torch.rand(L, L, L, generator=g)
+    R = _three_rotations()[:nrot]
+    R0 = torch.from_numpy(R[:1])
+    norm64 = orc.correlate_fft(recf[None, None], orc.rotate_volume(ligf[None, None], R0, dtype=torch.float64), dtype=torch.float64)
+    thr = float(norm64.median())
+    clip = 5.0
+    if biting_clip:
+        a = orc.correlate_fft(rec[0], orc.rotate_volume(lig[0], R0.float())).abs().reshape(-1)
+        clip = float(a.kthvalue(int(0.9 * a.numel())).values)
+        share = float((a > clip).double().mean())
+        assert 0.05 <= share <= 0.2, ("clipped share", share)
+    torch.manual_seed(6)
+    filt = SimpleFilter(list(sizes))
+    model = GlobalDockingModel(SyntheticRepr(tuple(sizes)), filt, threshold_clash=thr, clip=clip, lib=lib)
+    W = [w.cpu() for w in filt.parameters_tuple()]
+    want, Vs = orc.dock_volumes(rec, lig, recf[None, None], ligf[None, None], R, *W, thr, K, clip=clip, faithful_topk=False,
+                                return_V=True)
+    # the oracle's own list must be worth comparing with, before anything is compared
+    assert len({w[4] for w in want}) >= K // 2, "the list must rank distinct scores"
+    masked = float(np.mean([float((v == 0).float().mean()) for v in Vs]))
+    assert 0.2 <= masked <= 0.7, ("masked fraction", masked)
+    assert want[0][4] < 0
+    if biting_clip:
+        unclipped = orc.dock_volumes(rec, lig, recf[None, None], ligf[None, None], R, *W, thr, K, clip=5.0, faithful_topk=False)
+        assert unclipped != want, "the clip does not change the list"
+    scale = max(float(v.abs().max()) for v in Vs)
+    dk = Docker(model.to(device), box_size=L, max_conf=K, rotations=R, device=device, lib=lib)
+    got = dk.dock_volumes(rec, lig, recf, ligf, batch_size=2, write=False)
+    assert dk.path == "ops" and dk.engine is None
+    worst = max(abs(a[4] - b[4]) for a, b in zip(got, want)) / (1e-4 * scale)
+    near = _near_entries(want, 1e-4 * scale)
+    moved = _check_lists_band(got, want, scale, K)
+    print("box %d %s, %d rotation(s), clip %.3g: worst score difference %.3g of the band, %d moved / %d near, masked %.2f, "
+          "%d distinct scores, rotations in the list %s" % (L, list(sizes), nrot, clip, worst, moved, near, masked,
+                                                           len({w[4] for w in want}), sorted({w[0] for w in want})), flush=True)
+    assert moved <= near
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L,sizes,nrot,biting_clip", [(84, [4], 2, True), (85, [2], 1, False), (96, [2, 3], 2, False), (128, [2], 1, False)])
+def test_boxes_above_80_search_on_the_stand_alone_ops_on_gpu(L, sizes, nrot, biting_clip):
+    """box 84: N = 168, a multiple of 4 -- the vectorised filter -- and the clip biting; box 85: N = 170, k_filter_generic;
+    box 96: [2 @ 96^3, 3 @ 48^3], the fine grid plan-free, the coarse one inside the 64 plan, upsample factor 2; box 128: the
+    top of the range, the top-K over 256^3 candidates."""
+    import __graft_entry__ as entry
+    entry.build()
+    _run_box_above_80(None, torch.device("cuda:0"), L, sizes, nrot, 100, biting_clip=biting_clip)
 
 
 def _run_embedded_two_resolutions(lib, device, L, C0, C1, K):

@@ -147,7 +147,25 @@ def test_volume_convolution(dev, L, C, embed):
     acc.check_volume_convolution(None, dev, L, C=C, embed=embed, seed=30 + L)
 
 
-@pytest.mark.parametrize("L,C", [(32, 3), (80, 2)])
+@pytest.mark.parametrize("L,C,inputs", [(65, 2, None), (84, 2, None), (127, 1, ("dense", "impulse ligand", "impulse x impulse")),
+                                        (128, 1, ("dense", "impulse ligand", "impulse x impulse"))])
+def test_volume_convolution_plan_free_above_64_kb_of_lds(dev, L, C, inputs):
+    """The boxes that reach the plan-free route in normal use (81 .. 128; 65 .. 80 are embedded by default), where the tile of
+    its middle-axis transform, (n_in * 64 + N) * 8 bytes, exceeds the 64 KB a kernel gets unasked: box 65 (N = 130, 67,600 B:
+    the smallest, and N % 4 != 0 runs the k0 + u < N tail), 84 (N = 168), 127 (odd, N = 254), 128 (the largest box of the
+    route, 133,120 B).  The yardstick and its formulation factor sqrt(N / log2 N) as check_volume_convolution derives them."""
+    acc.check_volume_convolution(None, dev, L, C=C, embed=False, seed=30 + L, inputs=inputs)
+
+
+def test_volume_convolution_plan_free_chunks_at_box_128(dev):
+    acc.check_plan_free_chunks(None, dev, 128, 12, seed=31)
+
+
+def test_volume_convolution_plan_free_clamp_bites(dev):
+    acc.check_plan_free_clamp(None, dev, 84, 2, seed=32)
+
+
+@pytest.mark.parametrize("L,C", [(32, 3), (80, 2), (127, 1)])
 def test_volume_rotation(dev, L, C):
     acc.check_volume_rotation(None, dev, L, C=C, seed=40 + L)
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import docking_oracle as orc
+import local_checks as lc
 
 TOL = 1e-4
 EPS = 2.0 ** -24
@@ -33,28 +34,7 @@ def _rots(n, seed=1):
 # ---------------------------------------------------------------------------------------------- 1: MultiplyVolumes vs G1
 def test_multiply_volumes_reproduces_the_reference_module(golden, emu):
     from deeplocalproteindocking_amd.ops import MultiplyVolumes
-    g = golden("g1_multiply_volumes.npz")
-    mv = MultiplyVolumes(lib=emu)
-    for L, count in ((4, 343), (6, 1331)):
-        v1, v2 = torch.from_numpy(g["v1_L%d" % L]), torch.from_numpy(g["v2_L%d" % L])
-        T = torch.from_numpy(g["T_L%d" % L]).float()
-        assert T.shape[0] == count
-        B = T.shape[0]
-        got = mv(v1.expand(B, -1, -1, -1, -1).contiguous(), v2.expand(B, -1, -1, -1, -1).contiguous(), T).numpy()
-        mag = orc.correlate_direct(np.abs(v1.numpy()), np.abs(v2.numpy()))[0]                 # sum |v1 v2| per translation
-        N = 2 * L
-        bound = np.stack([mag[(slice(None),) + _signed_index(t, N)] for t in g["T_L%d" % L]]) * 2 * (L ** 3 + 1) * EPS
-        assert got.shape == g["out_L%d" % L].shape
-        assert (np.abs(got - g["out_L%d" % L]) <= bound).all()
-        assert np.abs(g["out_L%d" % L]).max() > 1.0
-    # fractional rows: int() truncates toward zero
-    v1 = torch.from_numpy(g["v1_L6"]).repeat(2, 1, 1, 1, 1)
-    v2 = torch.from_numpy(g["v2_L6"]).repeat(2, 1, 1, 1, 1)
-    got = mv(v1, v2, torch.from_numpy(g["Tfrac"])).numpy()
-    mag = orc.correlate_direct(np.abs(g["v1_L6"]), np.abs(g["v2_L6"]))[0]
-    tt = np.trunc(g["Tfrac"]).astype(int)
-    bound = np.stack([mag[(slice(None),) + _signed_index(t, 12)] for t in tt]) * 2 * (6 ** 3 + 1) * EPS
-    assert (np.abs(got - g["out_frac"]) <= bound).all()
+    v1, v2 = lc.check_multiply_volumes_g1(emu, "cpu", golden("g1_multiply_volumes.npz"))
     with pytest.raises(RuntimeError, match="no CPU path"):
         MultiplyVolumes()(v1, v2, torch.zeros(2, 3))
 
@@ -99,23 +79,7 @@ def test_local_correlate_matches_oracle(emu, L, C, r):
 
 def test_local_correlate_given_volumes_per_pose_and_coarse_modes(emu):
     """R = null (volumes as they are), one volume pair per pose, and the two coarse conventions on a half-resolution grid."""
-    from deeplocalproteindocking_amd import ops
-    L, C, P = 6, 2, 6
-    g = torch.Generator().manual_seed(77)
-    rec, lig = torch.randn(P, C, L, L, L, generator=g), torch.randn(P, C, L, L, L, generator=g)
-    T = torch.tensor([[-3, 5, -1], [-7, 3, 9], [1, -1, -5], [0, 0, 0], [-11, 11, -9], [-1, 1, -3]], dtype=torch.int32)
-    for mode, fn in (("floor", np.floor), ("trunc", np.trunc)):
-        got = ops.local_correlate(rec, lig, T, radius=0, scale=2, coarse=mode, lib=emu).reshape(P, C)
-        for p in range(P):
-            t = fn(T[p].numpy() / 2.0).astype(int)
-            full = orc.correlate_direct(rec[p:p + 1].numpy(), lig[p:p + 1].numpy())[0]
-            mag = orc.correlate_direct(np.abs(rec[p:p + 1].numpy()), np.abs(lig[p:p + 1].numpy()))[0]
-            idx = (slice(None),) + _signed_index(t, 2 * L)
-            want = full[idx] if (np.abs(t) < L).all() else np.zeros(C)
-            assert (np.abs(got[p].numpy() - want) <= 2 * (L ** 3 + 1) * EPS * mag[idx]).all()
-    a = ops.local_correlate(rec, lig, T, radius=0, scale=2, coarse="floor", lib=emu)
-    b = ops.local_correlate(rec, lig, T, radius=0, scale=2, coarse="trunc", lib=emu)
-    assert not torch.equal(a, b)                        # negative odd components tell the two apart
+    lc.check_given_volumes_per_pose_and_coarse_modes(emu, "cpu", L=6)
 
 
 def test_local_correlate_launch_grid_limit(emu):
@@ -304,66 +268,21 @@ def test_score_poses_calls_any_other_filter_on_the_features(emu):
 def test_local_filter_minimum_per_pose_lowest_index_wins_a_tie(emu):
     """dlpd_local_filter's per-pose minimum against numpy on the scores it wrote (argmin: first occurrence), with windows of
     more voxels than a wave has lanes, ties among masked (zero) scores, and a filter too wide for the kernel."""
-    from deeplocalproteindocking_amd import ops
-    g = torch.Generator().manual_seed(8)
-    P, C0, C1, r = 5, 3, 2, 2
-    W = 2 * r + 1
-    corr0, corr1 = torch.randn(P, C0, W, W, W, generator=g), torch.randn(P, C1, 3, 3, 3, generator=g)
-    clash = torch.rand(P, W, W, W, generator=g)
-    clash[1] = 2.0                                       # every voxel of pose 1 masked: all scores 0, index 0 wins
-    T = torch.tensor([[-3, 5, -1], [0, 0, 0], [1, -1, 7], [-7, -7, -7], [2, 4, 6]], dtype=torch.int32)
-    W1, b1 = torch.randn(2, C0 + C1, generator=g), torch.randn(2, generator=g)
-    W2, b2 = -torch.rand(1, 2, generator=g), torch.tensor([0.5])
-    score, best, besti = ops.local_filter(corr0, corr1, clash, T, r, W1, b1, W2, b2, scale=2, clip=0.7, threshold=0.6, lib=emu)
-    feat = ops.local_features(corr0, corr1, T, r, scale=2, clip=0.7)
-    want = (orc.filter_mlp(feat, W1, b1, W2, b2).reshape(P, W, W, W) * (clash < 0.6).float()).numpy()
-    assert np.abs(score.numpy() - want).max() <= 1e-6 * np.abs(want).max()
-    flat = score.numpy().reshape(P, -1)
-    assert besti.tolist() == np.argmin(flat, axis=1).tolist() and besti[1] == 0
-    assert best.numpy().tobytes() == flat[np.arange(P), np.argmin(flat, axis=1)].tobytes()
-    assert (flat == 0).any() and (flat < 0).any()
-    wide = ops.local_filter(corr0, corr1, clash, T, r, torch.randn(40, C0 + C1), torch.randn(40), torch.randn(1, 40), b2, scale=2, lib=emu)
-    assert wide is None                                   # hidden width beyond the kernel's: the caller applies its module
+    lc.check_filter_minimum_per_pose(emu, "cpu", r=2, coarse="floor", H=2)
 
 
 # ---------------------------------------------------------------------------------------------- 4: LocalDockingModel vs G8
-def _g8():
-    from conftest import GOLDEN
-    return np.load(os.path.join(GOLDEN, "local", "g8_local_forward.npz"))
-
-
-def _g8_filter(g):
-    from deeplocalproteindocking_amd.Models import SimpleFilter
-    filt = SimpleFilter(g["num_outputs"].tolist())
-    keys = json.loads(bytes(g["filter_keys"]).decode())
-    assert list(filt.state_dict().keys()) == keys
-    filt.load_state_dict({k: torch.from_numpy(g["filter_sd_" + k]) for k in keys}, strict=True)
-    return filt.eval()
-
-
 def test_local_docking_model_reproduces_the_reference_forward(emu):
     from deeplocalproteindocking_amd.Models import E3MultiResRepr4x4, LocalDockingModel
-    g = _g8()
+    g = lc.g8()
     rec, lig, T = torch.from_numpy(g["receptor"]), torch.from_numpy(g["ligand"]), torch.from_numpy(g["T"])
     want = g["out"]
-    band = TOL * np.abs(want).max()
-    assert (np.abs(T.numpy()) >= rec.shape[2]).any() and (T.numpy() != np.trunc(T.numpy())).any()
-
-    class Recorded(torch.nn.Module):                     # isolates the new kernels and the trunc convention
-        def forward(self, x):
-            tag = "rec" if x is rec else "lig"
-            return [torch.from_numpy(g["%s_vol%d" % (tag, i)]) for i in range(2)]
-    stub = LocalDockingModel(Recorded(), _g8_filter(g), lib=emu).eval()
-    with torch.no_grad():
-        got = stub(rec, lig, T).numpy()
-    print("LocalDockingModel (recorded volumes): max error %.3g, band %.3g" % (np.abs(got - want).max(), band))
-    assert got.shape == want.shape == (rec.shape[0], 1)
-    assert np.abs(got - want).max() <= band
+    band = lc.check_local_model_on_recorded_volumes(emu, "cpu", g)
     # the whole call: this build's representation with the recorded weights
     net = E3MultiResRepr4x4(multiplier=1).eval()
     keys = json.loads(bytes(g["repr_keys"]).decode())
     net.load_state_dict({k: torch.from_numpy(g["repr_sd_" + k]) for k in keys}, strict=True)
-    model = LocalDockingModel(net, _g8_filter(g), lib=emu).eval()
+    model = LocalDockingModel(net, lc.g8_filter(g), lib=emu).eval()
     with torch.no_grad():
         got = model(rec, lig, T).numpy()
     print("LocalDockingModel (whole call): max error %.3g, band %.3g" % (np.abs(got - want).max(), band))

@@ -2,12 +2,15 @@
 ([16@80^3, 32@40^3]) and at 48@64^3, on dense random and on protein-shaped (mostly zero) volumes.  Expected values are
 float64 direct sums over the window (no 160^3 transform needed); the rotated ligand is the CPU oracle's.  Tolerances as in
 test_local_emu.py: the f32 summation bound 2 (K + 1) 2^-24 sum|v1 v2| plus the parity band 1e-4 of the largest value
-compared.  Nothing here reads the reference tree."""
+compared.  Beyond those shapes: the correlation at boxes 33 / 96 / 127 / 128 (the ends of its launch geometry), one volume
+pair per pose and the coarse conventions, the filter kernel over windows of 5^3 and 7^3, and the reference's recorded outputs
+G1 / G8 -- check bodies in tests/local_checks.py, shared with test_local_emu.py.  Nothing here reads the reference tree."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import docking_oracle as orc
+import local_checks as lc
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -67,11 +70,18 @@ def _translations(P, L, seed):
     return T
 
 
-@pytest.mark.parametrize("L,C,r,kind", [(80, 16, 1, "dense"), (80, 16, 1, "protein"), (40, 32, 2, "dense"), (40, 32, 0, "protein"),
-                                        (64, 48, 1, "dense"), (64, 48, 1, "protein"), (40, 4, 3, "dense"), (64, 5, 2, "protein")])
-def test_local_correlate_matches_float64_direct_sums(dev, L, C, r, kind):
+# (L, C, r, kind, P).  Beside the reference's shapes, the shapes the backward already has (test_local_grad_gpu.py) and the
+# ends of the launch geometry (csrc/dlpd_local.h, local_xt): box 33 -> 7 x-planes per block, 231 of 256 threads, a last slab
+# of 5 planes, r = 3 -> one dx per block (grid.y = 7); box 127 -> 2 planes, 254 threads, 64 slabs, the last of ONE plane;
+# box 128 -> DLPD_LOCAL_MAXL.  Three poses at boxes >= 96: the float64 sums on the host are what a case costs.
+CORRELATE_CASES = [(80, 16, 1, "dense", 8), (80, 16, 1, "protein", 8), (40, 32, 2, "dense", 8), (40, 32, 0, "protein", 8),
+                   (64, 48, 1, "dense", 8), (64, 48, 1, "protein", 8), (40, 4, 3, "dense", 8), (64, 5, 2, "protein", 8),
+                   (33, 3, 3, "dense", 8), (96, 2, 1, "protein", 3), (127, 2, 1, "dense", 3), (128, 2, 0, "dense", 3)]
+
+
+@pytest.mark.parametrize("L,C,r,kind,P", CORRELATE_CASES, ids=["%d-%d-%d-%s" % c[:4] for c in CORRELATE_CASES])
+def test_local_correlate_matches_float64_direct_sums(dev, L, C, r, kind, P):
     from deeplocalproteindocking_amd import ops
-    P = 8
     rec, lig = _volume(C, L, 100 + L + C, kind), _volume(C, L, 200 + L + C, kind)
     R = torch.from_numpy(_rots(P, seed=L + r)).float().contiguous()
     T = _translations(P, L, seed=3 * L + r)
@@ -117,6 +127,34 @@ def test_local_correlate_batches_a_list_beyond_the_launch_grid_limit(dev):
     assert float(got.abs().min()) > 0.0
 
 
+@pytest.mark.parametrize("L", [6, 33])
+def test_local_correlate_given_volumes_per_pose_and_coarse_modes(dev, L):
+    """One volume pair per pose, R = null, scale 2, "floor" against "trunc" on negative odd components: at the emulator's
+    box 6 (36 of 256 threads active) and at box 33."""
+    lc.check_given_volumes_per_pose_and_coarse_modes(None, dev, L=L)
+
+
+@pytest.mark.parametrize("H", [2, 5, 32])
+@pytest.mark.parametrize("coarse", ["floor", "trunc"])
+@pytest.mark.parametrize("r", [2, 3])
+def test_local_filter_minimum_per_pose_lowest_index_wins_a_tie(dev, r, coarse, H):
+    """k_local_filter beyond one trip of its 64-lane loop: the coarse index of scale 2 under both conventions, hidden widths 2,
+    5 (padded to 8) and 32, and the wave's lowest-index-wins reduction (an all-masked pose: 125 / 343 tied zeros, index 0)."""
+    lc.check_filter_minimum_per_pose(None, dev, r=r, coarse=coarse, H=H)
+
+
+def test_multiply_volumes_reproduces_the_reference_module(dev, golden):
+    """G1 on the device: boxes 4 and 6, where 16 / 36 of a block's 256 threads are active."""
+    lc.check_multiply_volumes_g1(None, dev, golden("g1_multiply_volumes.npz"))
+
+
+def test_local_docking_model_reproduces_the_reference_forward_on_recorded_volumes(dev):
+    """G8 on the device, the half that needs no representation: the reference's recorded volumes (boxes 12 and 6), fractional
+    and out-of-box T, the trunc convention.  (The whole call stays on the emulator: the fixture's representation has 2 and 4
+    output channels, which the HIP convolution rejects by design.)"""
+    lc.check_local_model_on_recorded_volumes(None, dev, lc.g8())
+
+
 def _model(sizes, thr, clip, dev, seed=3):
     from deeplocalproteindocking_amd.Models import GlobalDockingModel, SimpleFilter
     torch.manual_seed(seed)
@@ -138,11 +176,18 @@ def _score64(rec, lig_rot, W, tau, clip):
     return float(W2.reshape(-1) @ np.maximum(W1 @ np.concatenate(feats) + b1, 0.0) + b2.reshape(-1)[0])
 
 
-@pytest.mark.parametrize("sizes,L,kind,clip", [([16, 32], 80, "dense", 5.0), ([16, 32], 80, "protein", 0.5), ([48], 64, "dense", 5.0),
-                                               ([48], 64, "protein", 5.0)])
-def test_score_poses_matches_float64_direct_sums(dev, sizes, L, kind, clip):
+# (sizes, L, kind, clip, r).  The last two: the whole window of the filter kernel (r = 2: 125 entries, two trips of its 64-lane
+# loop; r = 3: 343, six) with the coarse window of the second resolution, on the smallest box that holds them.
+SCORE_CASES = [([16, 32], 80, "dense", 5.0, 1), ([16, 32], 80, "protein", 0.5, 1), ([48], 64, "dense", 5.0, 1), ([48], 64, "protein", 5.0, 1),
+               ([4, 6], 24, "dense", 0.5, 2), ([4, 6], 24, "dense", 0.5, 3)]
+SCORE_IDS = ["sizes0-80-dense-5.0", "sizes1-80-protein-0.5", "sizes2-64-dense-5.0", "sizes3-64-protein-5.0", "sizes4-24-dense-0.5-r2",
+             "sizes5-24-dense-0.5-r3"]
+
+
+@pytest.mark.parametrize("sizes,L,kind,clip,r", SCORE_CASES, ids=SCORE_IDS)
+def test_score_poses_matches_float64_direct_sums(dev, sizes, L, kind, clip, r):
     from deeplocalproteindocking_amd.Docker import Docker
-    P, r = 8, 1
+    P = 8
     amp = 0.02 if kind == "dense" else 0.05
     rec = [_volume(c, L >> i, 300 + c, kind, amp) for i, c in enumerate(sizes)]
     lig = [_volume(c, L >> i, 400 + c, kind, amp) for i, c in enumerate(sizes)]
