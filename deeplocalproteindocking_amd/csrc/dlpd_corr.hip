@@ -29,14 +29,6 @@
 #define DLPD_K1CL_PXOR 0                 // diagnostic builds only (EXPERIMENTS.md R5)
 #endif
 #define DLPD_K1_UNROLL 2                 // samples per thread whose gathers are issued together (2..16 measured equal: not latency-bound)
-template <int N> DLPD_D void init_twiddles(cplx* tw, int tid, int nthreads) {
-  for (int k = tid; k < N; k += nthreads) {
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)N, &s, &c);
-    tw[k] = c_make((float)c, (float)s);
-  }
-}
-
 // Same sample from the QUAD layout of a volume: q[x][y][z] (y, z < L-1) = {v(x,y,z), v(x,y,z+1), v(x,y+1,z),
 // v(x,y+1,z+1)} as one float4, so the eight corners are TWO 16-byte gathers instead of four 8-byte ones: the
 // gather is bound by the number of cache lines its instructions touch, and this halves the instructions.
@@ -494,7 +486,10 @@ template <int MODE> struct K3Cfg<80, MODE> { static constexpr int NT = (MODE == 
 template <> struct K3Cfg<160, 0> { static constexpr int NT = 320, WC = 5, TY = 16; };
 // N = 160, fused: five waves own the channels' transforms, TEN accumulate (2 voxels per thread): with the two-pass
 // z transform the accumulation is the longer phase and the extra waves pay (2.90 -> 2.63 ms at the real shapes;
-// with the three-pass transform they did not: 3.96 vs 3.71 ms)
+// with the three-pass transform they did not: 3.96 vs 3.71 ms).  The 2.63 ms were measured on k_zifft_filter_tiles, a second
+// copy of this kernel whose blocks walked all y-tiles of an x' plane; it was removed once the role-split kernel was the
+// product at N = 160 and this formulation only its bit-exactness reference, which needs the same fmaf chains and not the tile
+// walk (the code: git show 7c60625:deeplocalproteindocking_amd/csrc/dlpd_corr.hip, the record: profiles/r02_i_real_shapes_*).
 #ifndef DLPD_K3_160_NT
 #define DLPD_K3_160_NT 640
 #endif
@@ -511,15 +506,16 @@ k_zifft_filter(const cplx* __restrict__ Bw, float* __restrict__ out, int CT, int
                const float* __restrict__ W1t, const float* __restrict__ b1, const float* __restrict__ W2,
                float b2, int has_clip, float clip, float thr, K3Aux aux, K3Cand cd) {
   typedef K3Cfg<N, MODE> Cfg;
-  constexpr int NZ = N / 2 + 1, RS = N + 8, TY = Cfg::TY, NPAIR = TY / 2;
+  typedef K3Lds<N, Cfg> Geo;                   // (dlpd_k3.h: shared with launch_k3)
+  constexpr int NZ = Geo::NZ, RS = Geo::RS, TY = Cfg::TY, NPAIR = Geo::NPAIR;
   constexpr int NT = Cfg::NT, WC = Cfg::WC;
-  constexpr int CPW = 8 / NPAIR;               // channels per wave: its 8 pencils = CPW channels x NPAIR row pairs
-  constexpr int LPK = 64 / NPAIR;              // kz rows per 64-lane DMA instruction
+  constexpr int CPW = Geo::CPW;                // channels per wave: its 8 pencils = CPW channels x NPAIR row pairs
+  constexpr int LPK = Geo::LPK;                // kz rows per 64-lane DMA instruction
   static_assert((NPAIR == 8 || NPAIR == 4) && WC * 64 <= NT, "one wave = 8 pencils x 8 threads");
   constexpr int EPT = (NPAIR * N) / NT > 0 ? (NPAIR * N) / NT : 1;   // complex outputs per thread per channel
   constexpr int MSTEP = NT / N;                // pair stride between a thread's outputs
   static_assert((NPAIR * N) % NT == 0 || NPAIR * N < NT, "tile/thread mismatch");
-  constexpr int RAWC = ((NZ * NPAIR + 63) / 64) * 64;    // float4 slots per channel (whole waves)
+  constexpr int RAWC = Geo::RAWC;              // float4 slots per channel (whole waves)
   DLPD_DYN_SHARED(cplx, S);
   cplx* tw = S + WC * 8 * RS;
   float4* raw = reinterpret_cast<float4*>(tw + N);        // [WC][CPW][RAWC] staging of raw spectra
@@ -797,299 +793,6 @@ k_zifft_filter(const cplx* __restrict__ Bw, float* __restrict__ out, int CT, int
 }
 
 // ------------------------------------------------------------------------------------------
-// K3 walking several tiles per block (MODE 1 only).  With few channels per tile (the reference's real model:
-// 17 channels = 2 groups at N = 160) a third of a one-tile block is the exposed latency of its first DMA
-// (stamps: dma_wait 33 %); here a block takes `tpb` consecutive tiles (all y-tiles of one x') and the first group
-// of the NEXT tile streams in behind the last group of the current one.  ONE loop over (tile, group) steps, not a
-// tile loop around a group loop, and lane-dependent offsets made opaque per step: otherwise the compiler hoists
-// another ~20 VGPRs of addressing next to the 96 accumulators and spills.  Not used at N <= 128, where 7 groups per
-// tile hide that latency already and the extra register pressure costs more (measured 2.51-2.57 vs 2.40 ms).
-// ------------------------------------------------------------------------------------------
-template <int N, int HP, int MODE> __global__ void __launch_bounds__((K3Cfg<N, MODE>::NT))
-k_zifft_filter_tiles(const cplx* __restrict__ Bw, float* __restrict__ out, int CT, int C, int has_clash, int G,
-               const float* __restrict__ W1t, const float* __restrict__ b1, const float* __restrict__ W2,
-               float b2, int has_clip, float clip, float thr, K3Aux aux, int ntiles, int tpb, K3Cand cd) {
-  typedef K3Cfg<N, MODE> Cfg;
-  constexpr int NZ = N / 2 + 1, RS = N + 8, TY = Cfg::TY, NPAIR = TY / 2;
-  constexpr int NT = Cfg::NT, WC = Cfg::WC, NYT = N / TY;
-  constexpr int CPW = 8 / NPAIR;               // channels per wave: its 8 pencils = CPW channels x NPAIR row pairs
-  constexpr int LPK = 64 / NPAIR;              // kz rows per 64-lane DMA instruction
-  static_assert((NPAIR == 8 || NPAIR == 4) && WC * 64 <= NT, "one wave = 8 pencils x 8 threads");
-  constexpr int EPT = (NPAIR * N) / NT > 0 ? (NPAIR * N) / NT : 1;   // complex outputs per thread per channel
-  constexpr int MSTEP = NT / N;                // pair stride between a thread's outputs
-  static_assert((NPAIR * N) % NT == 0 || NPAIR * N < NT, "tile/thread mismatch");
-  constexpr int RAWC = ((NZ * NPAIR + 63) / 64) * 64;    // float4 slots per channel (whole waves)
-  DLPD_DYN_SHARED(cplx, S);
-  cplx* tw = S + WC * 8 * RS;
-  float4* raw = reinterpret_cast<float4*>(tw + N);        // [WC][CPW][RAWC] staging of raw spectra
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t_beg = blockIdx.x * tpb, t_end = (t_beg + tpb < ntiles) ? t_beg + tpb : ntiles;
-  if (t_beg >= t_end) return;
-  init_twiddles<N>(tw, tid, NT);
-
-  // candidate filter of the top-K stage (0: none valid yet -> the rotation is flagged for the full select)
-  const unsigned cand_tau = (MODE == 1 && cd.keys) ? *cd.tau : 0u;
-  const int zz = tid % N, m0 = tid / N;        // output ownership
-  const bool owner = (NPAIR * N >= NT) || (m0 < NPAIR);
-  const int tr = lane & 7, qr = lane >> 3;     // FFT: lane = 8*pencil + thread
-  float4* rawg = raw + wave * CPW * RAWC;
-
-  // this wave's channels of group `cb` of tile `t`: raw[k][m] <- Bw[b][cb + wave*CPW + j][k][xo][y0+2m .. +1]
-  // (lane = NPAIR*(k % LPK) + m: LPK runs of NPAIR*16 bytes per DMA instruction; k = N/2 is the last, short one)
-  constexpr int NFULL = (N / 2) / LPK;         // full 64-lane DMA instructions per channel (bins 0..N/2-1)
-  static_assert(NZ * NPAIR == NFULL * 64 + NPAIR, "raw channel = NFULL full DMA instructions + one short one");
-  auto issue_channel = [&](int t, int cb) {
-    const int ty0 = (t % NYT) * TY, txo = (t / NYT) % N, tb = t / (NYT * N);
-#pragma unroll
-    for (int j = 0; j < CPW; j++) {
-      const int g = wave * CPW + j;
-      if (g < G && cb + g < CT) {
-        const cplx* src = Bw + (((size_t)tb * CT + cb + g) * NZ * N + txo) * N + ty0;
-        const cplx* lane_src = src + (size_t)(lane / NPAIR) * N * N + 2 * (lane % NPAIR);
-        float4* rj = rawg + j * RAWC;
-#pragma unroll
-        for (int it = 0; it < NFULL; it++) DLPD_GLDS16(lane_src + (size_t)it * LPK * N * N, rj + it * 64);
-        const int mt = lane % NPAIR;                        // tail lanes re-read valid elements
-        DLPD_GLDS16(src + (size_t)(N / 2) * N * N + 2 * mt, rj + NFULL * 64);
-      }
-    }
-  };
-  DLPD_STAMP_DECL;
-  issue_channel(t_beg, 0);
-  __syncthreads();                             // twiddle table visible
-
-  // ONE loop over (tile, channel group) steps -- not a tile loop around a group loop: with a single loop level the
-  // compiler keeps the same values in registers as the one-tile kernel did (an outer tile loop made it hoist
-  // another ~20 VGPRs of addressing and spill next to the 96 accumulators)
-  float nrm[EPT * 2];
-  float h[EPT * 2][HP > 0 ? HP : 1];
-  const int ngroups = (CT + G - 1) / G;
-  int t = t_beg, cbase = 0;
-#pragma unroll 1
-  for (int step = 0, nsteps = (t_end - t_beg) * ngroups; step < nsteps; step++) {
-  const int y0 = (t % NYT) * TY, xo = (t / NYT) % N, b = t / (NYT * N);
-  if (cbase == 0) {
-  if (cd.keys && !cand_tau && tid == 0) cd.count[cd.nb + b] = 1u;
-  // hidden pre-activations of the thread's 2*EPT voxels (the SLP vectoriser pairs adjacent
-  // hidden units into v_pk_fma_f32 with the weight pair in SGPRs and the voxel value broadcast)
-#pragma unroll
-  for (int e = 0; e < EPT * 2; e++) nrm[e] = 0.f;
-  if (MODE == 1) {
-    if (aux.C > 0 && aux.is_preact) {
-      // rows 2m, 2m+1 and columns z, z^1 of the fine grid share one coarse voxel
-      const int Na = aux.N;
-      const size_t cstride = (size_t)Na * Na * Na;
-      const float* ab = aux.p + (size_t)b * HP * cstride + ((size_t)(xo >> 1) * Na + (y0 >> 1)) * Na + (zz >> 1);
-      if (owner) {
-#pragma unroll
-        for (int e = 0; e < EPT; e++)
-#pragma unroll
-          for (int j = 0; j < HP; j++) {
-            const float v = ab[(size_t)j * cstride + (size_t)(m0 + e * MSTEP) * Na];
-            h[2 * e][j] = v;
-            h[2 * e + 1][j] = v;
-          }
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < EPT * 2; e++)
-#pragma unroll
-        for (int j = 0; j < HP; j++) h[e][j] = b1[j];
-    }
-  }
-  }
-
-  {
-    const int gn = (CT - cbase) < G ? (CT - cbase) : G;
-    if (wave * CPW < gn) {
-      DLPD_WAIT_VMEM();                        // this wave's own DMA has landed
-      DLPD_WAVE_SYNC();
-      DLPD_STAMP(0);
-      // pack two rows per complex pencil: Z[k] = A[k] + i B[k], Z[N-k] = conj(A[k]) + i conj(B[k])
-      // Lane -> (pencil m, kz row) of the element it packs.  The DMA layout of `raw` is [it][kq][m] (slot =
-      // NPAIR*kq + m inside the 64-slot block of DMA instruction `it`, k = LPK*it + kq).  Packing in that same
-      // lane order makes a 16-lane store group hit 8 pencils x 2 k: the pencil stride (RS = N + 8 complex = 16
-      // dwords mod 32) leaves only 8 distinct banks, a 4-way conflict on every ds_write_b64 (a third of this
-      // kernel's LDS cycles, SQ_LDS_BANK_CONFLICT).  For NPAIR = 8 the lanes are therefore re-dealt so that a
-      // store group covers 4 pencils x 4 consecutive-block k and every lane additionally walks the DMA
-      // instructions rotated by 2m: found by exhaustive search over lane-bit permutations x rotations
-      // (model of the ds_write_b64 / ds_read_b128 lane groups, MI355X_MICROARCH.md LDS table): raw reads stay
-      // conflict-free, stores cost 5.0 instead of 16.25 LDS cycles.
-#pragma unroll
-      for (int j = 0; j < CPW; j++) {
-        if (wave * CPW + j >= gn) break;
-        int m, kq, lq = lane;
-        if (1) DLPD_OPAQUE(lq);            // (pack offsets recomputed per group, not kept in VGPRs)
-        if (NPAIR == 8) {
-          m = (lq & 3) | (((lq >> 4) & 1) << 2);
-          kq = ((lq >> 2) & 1) | (((lq >> 5) & 1) << 1) | (((lq >> 3) & 1) << 2);
-        } else {
-          m = lq % NPAIR;
-          kq = lq / NPAIR;
-        }
-        const int rot = (NPAIR == 8) ? 2 * m : 0;            // lane-dependent start of its walk over the DMA instructions
-        const int slot = NPAIR * kq + m;
-        cplx* P = S + (wave * 8 + j * NPAIR + m) * RS;
-        const float4* rj = rawg + j * RAWC;
-        constexpr int PCH = NFULL > 8 ? NFULL / 2 : NFULL;   // raw elements in flight per lane
-        const float4 qh = rj[NFULL * 64 + (lane % NPAIR)];  // k = N/2 (lanes with lane / NPAIR == 0 store it)
-#pragma unroll
-        for (int it0 = 0; it0 < NFULL; it0 += PCH) {
-          float4 q[PCH];
-#pragma unroll
-          for (int u = 0; u < PCH; u++) q[u] = rj[((it0 + u + rot) % NFULL) * 64 + slot];
-#pragma unroll
-          for (int u = 0; u < PCH; u++) {
-            const int k = ((it0 + u + rot) % NFULL) * LPK + kq;
-            // k = 0: the purely real bin of both rows (both stores then write the same value to the same place)
-            const cplx lo = (k == 0) ? c_make(q[u].x, q[u].z) : c_make(q[u].x - q[u].w, q[u].y + q[u].z);
-            const cplx hi = (k == 0) ? c_make(q[u].x, q[u].z) : c_make(q[u].x + q[u].w, q[u].z - q[u].y);
-            P[pencil_in_pos<N>(k)] = lo;
-            P[pencil_in_pos<N>((N - k) & (k == 0 ? 0 : ~0))] = hi;
-          }
-        }
-        if (lane / NPAIR == 0) S[(wave * 8 + j * NPAIR + lane % NPAIR) * RS + pencil_in_pos<N>(N / 2)] = c_make(qh.x, qh.z);
-      }
-      DLPD_WAIT_LDS();                         // raw fully read before it is refilled
-      DLPD_WAVE_SYNC();
-    }
-    DLPD_STAMP(1);
-    // the next DMA streams in behind the math: the next group of this tile, or the first group of the next tile
-    if (cbase + G < CT) issue_channel(t, cbase + G);
-    else if (t + 1 < t_end) issue_channel(t + 1, 0);
-    DLPD_STAMP(2);
-    if (wave * CPW < gn) {
-      // lane-dependent offsets made opaque per group: otherwise the ~60 swizzled pencil offsets of the two
-      // passes are hoisted out of the group / tile loops and live in VGPRs next to the 96 accumulators (spills)
-      int tq = tr, qq = qr;
-      if (1) { DLPD_OPAQUE(tq); DLPD_OPAQUE(qq); }
-      fft_wave_pencils<N, +1>(S, wave * 8, RS, qq, tq, tw);
-    }
-    DLPD_STAMP(3);
-    DLPD_LDS_BARRIER();                        // all channels of the group transformed
-    DLPD_STAMP(4);
-    if (owner) {
-      if (MODE == 0) {
-        for (int g = 0; g < gn; g++) {
-          const int c = cbase + g;
-#pragma unroll
-          for (int e = 0; e < EPT; e++) {
-            const int m = m0 + e * MSTEP;
-            const cplx val = S[(g * NPAIR + m) * RS + pencil_out_pos<N>(zz)];
-            float v0 = val.x, v1 = val.y;
-            if (has_clip && c < C) { v0 = DLPD_CLAMP(v0, clip); v1 = DLPD_CLAMP(v1, clip); }
-            float* o = out + ((((size_t)b * CT + c) * N + xo) * N + y0 + 2 * m) * N + zz;
-            o[0] = v0;
-            o[N] = v1;
-          }
-        }
-      } else {
-        // score channels of this group; the clash channel (index C, always last) is peeled off
-        const int gs = (cbase + gn <= C) ? gn : (C - cbase > 0 ? C - cbase : 0);
-        // first-layer weights are wave-uniform (scalar loads): channel g+1's row is requested
-        // before channel g's FMAs so the scalar-load latency hides behind them
-        float wcur[HP > 0 ? HP : 1], wnxt[HP > 0 ? HP : 1];
-        cplx vcur[EPT], vnxt[EPT];
-        if (gs > 0) {
-#pragma unroll
-          for (int j = 0; j < HP; j++) wcur[j] = W1t[(size_t)cbase * HP + j];
-#pragma unroll
-          for (int e = 0; e < EPT; e++) vcur[e] = S[(m0 + e * MSTEP) * RS + pencil_out_pos<N>(zz)];
-        }
-        for (int g = 0; g < gs; g++) {
-          // channel g+1's weights (scalar loads) and values (LDS) are requested here, one
-          // iteration ahead: both share lgkmcnt, so the only wait sits at the top of the next
-          // iteration, behind this channel's 96 FMAs
-          const int gn1 = (g + 1 < gs ? g + 1 : g);
-#pragma unroll
-          for (int j = 0; j < HP; j++) wnxt[j] = W1t[(size_t)(cbase + gn1) * HP + j];
-#pragma unroll
-          for (int e = 0; e < EPT; e++) vnxt[e] = S[(gn1 * NPAIR + m0 + e * MSTEP) * RS + pencil_out_pos<N>(zz)];
-          DLPD_SCHED_FENCE();
-#pragma unroll
-          for (int e = 0; e < EPT; e++) {
-            float v0 = vcur[e].x, v1 = vcur[e].y;
-            if (has_clip) { v0 = DLPD_CLAMP(v0, clip); v1 = DLPD_CLAMP(v1, clip); }
-#pragma unroll
-            for (int j = 0; j < HP; j++) {
-              h[2 * e][j] = fmaf(wcur[j], v0, h[2 * e][j]);
-              h[2 * e + 1][j] = fmaf(wcur[j], v1, h[2 * e + 1][j]);
-            }
-          }
-          DLPD_SCHED_FENCE();
-#pragma unroll
-          for (int j = 0; j < HP; j++) wcur[j] = wnxt[j];
-#pragma unroll
-          for (int e = 0; e < EPT; e++) vcur[e] = vnxt[e];
-        }
-        if (has_clash && cbase + gn > C) {
-          const int g = C - cbase;
-#pragma unroll
-          for (int e = 0; e < EPT; e++) {
-            const cplx v = S[(g * NPAIR + m0 + e * MSTEP) * RS + pencil_out_pos<N>(zz)];
-            nrm[2 * e] = v.x;
-            nrm[2 * e + 1] = v.y;
-          }
-        }
-      }
-    }
-    DLPD_STAMP(5);
-    DLPD_LDS_BARRIER();                        // pencils free for the next group
-    DLPD_STAMP(6);
-  }
-  if (cbase + G < CT) { cbase += G; continue; }          // more channel groups of this tile
-  if (MODE == 1 && owner && aux.C > 0 && !aux.is_preact) {
-    // coarse-resolution channels: rows 2m and 2m+1 and columns z, z^1 share one coarse voxel
-    const int Na = aux.N;
-    const float* ab = aux.p + (size_t)b * aux.C * Na * Na * Na + ((size_t)(xo >> 1) * Na + (y0 >> 1)) * Na + (zz >> 1);
-    constexpr int CH = EPT > 2 ? 4 : 8;       // channels per chunk: EPT*CH loads in flight per thread
-    const size_t cstride = (size_t)Na * Na * Na;
-    for (int cb = 0; cb < aux.C; cb += CH) {
-      float av[CH][EPT];
-#pragma unroll
-      for (int k = 0; k < CH; k++)
-#pragma unroll
-        for (int e = 0; e < EPT; e++)
-          av[k][e] = (cb + k < aux.C) ? ab[(size_t)(cb + k) * cstride + (size_t)(m0 + e * MSTEP) * Na] : 0.f;
-#pragma unroll
-      for (int k = 0; k < CH; k++) {
-        if (cb + k < aux.C) {
-          const float* w = W1t + (size_t)(C + cb + k) * HP;
-#pragma unroll
-          for (int e = 0; e < EPT; e++) {
-            const float v = av[k][e];
-#pragma unroll
-            for (int j = 0; j < HP; j++) {
-              h[2 * e][j] = fmaf(w[j], v, h[2 * e][j]);
-              h[2 * e + 1][j] = fmaf(w[j], v, h[2 * e + 1][j]);
-            }
-          }
-        }
-      }
-    }
-  }
-  if (MODE == 1 && owner) {
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-      const int m = m0 + e * MSTEP;
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        float acc = b2;
-#pragma unroll
-        for (int j = 0; j < HP; j++) acc = fmaf(W2[j], fmaxf(h[2 * e + u][j], 0.f), acc);
-        if (has_clash) acc = acc * ((nrm[2 * e + u] < thr) ? 1.0f : 0.0f);
-        out[(((size_t)b * N + xo) * N + y0 + 2 * m + u) * N + zz] = acc;
-        if (cd.keys && cand_tau) k3_emit(cd, cand_tau, b, (unsigned)((xo * N + y0 + 2 * m + u) * N + zz), acc);
-      }
-    }
-  }
-  cbase = 0;
-  t++;
-  }   // (tile, group) steps
-  DLPD_STAMP_FLUSH(dlpd_stamps, DLPD_STAMPS);
-}
-
-// ------------------------------------------------------------------------------------------
 // Generic filter over already materialised correlation volumes (multi-resolution path:
 // DockingModels.py:74-83).  conv_k (nb, C_k, N_k^3); nearest upsample index = i / (N/N_k).
 // ------------------------------------------------------------------------------------------
@@ -1308,6 +1011,18 @@ int dlpd_k3r_preact(const cplx* Bw, float* pre, int C, int nb, int L, const floa
 #ifndef DLPD_K3_DEFAULT_FORM
 #define DLPD_K3_DEFAULT_FORM 2               // 1: channel-owning waves (this file), 2: role-split waves (dlpd_k3r.hip)
 #endif
+// Boxes at which the fused modes of the channel-owning K3 (this file) are compiled.  The product library ships one formulation
+// per box: form 1 of the filter (MODE 1) where there is no role-split kernel, boxes 32 / 40, and its coarse-grid pre-activations
+// (MODE 2) at box 32 only -- box 40 takes the role-split kernel, and coarse grids of 64 / 80 have no fine grid.  The rest are
+// the bit-exactness reference of the role-split kernel, which covers every hidden width they have and leaves no default
+// path to them: compiled into tests/variants only.
+#ifdef DLPD_TEST_VARIANTS
+#define DLPD_K3_FORM1_BOXES DLPD_BOXES
+#define DLPD_K3_MODE2_BOXES DLPD_BOXES
+#else
+#define DLPD_K3_FORM1_BOXES 32, 40
+#define DLPD_K3_MODE2_BOXES 32
+#endif
 
 // K2 lives in dlpd_k2.hip (its own translation unit: it is built with -fno-slp-vectorize)
 int dlpd_k2_forward(const cplx* A, cplx* out, int CT, int nb, int L, float scale, hipStream_t st);
@@ -1319,77 +1034,20 @@ int dlpd_k2_pack_receptor(const cplx* rec, void* packed, int CT, int L, hipStrea
 int dlpd_k2_correlate_packed(const cplx* A, const cplx* packed, cplx* out, int CT, int nb, int L, hipStream_t st,
                              const unsigned char* pmap = nullptr, int nmasked = 0);
 
-// channels per group.  One channel per wave (16-row tiles, N <= 128): as many as there are channel-owning waves -- 49
-// channels on 8 waves are six full groups and one with the clash channel alone, 1 % faster than seven groups of seven,
-// which leave a wave idle in every transform phase.  Two channels per wave (8-row tiles, N = 160): balanced groups
-// (17 channels on 10 slots: 9 + 8 is 3 % faster than 10 + 7).
-static int k3_group(int CT, int maxg, bool balanced) {
-  if (!balanced) return CT < maxg ? CT : maxg;
-  const int ng = (CT + maxg - 1) / maxg;
-  return (CT + ng - 1) / ng;
-}
-
 template <int N, int HP, int MODE> static int launch_k3(const cplx* Bw, float* out, int CT, int C, int has_clash,
                                                         int nb, const float* W1t, const float* b1, const float* W2,
                                                         float b2, int has_clip, float clip, float thr,
                                                         hipStream_t st, K3Aux aux = K3Aux{nullptr, 0, 0, 0},
                                                         K3Cand cd = K3Cand{nullptr, nullptr, nullptr, 0, 0}) {
   typedef K3Cfg<N, MODE> Cfg;
-  constexpr int RS = N + 8, NZ = N / 2 + 1, W = Cfg::WC, NPAIR = Cfg::TY / 2, CPW = 8 / NPAIR;
-  constexpr int RAWC = ((NZ * NPAIR + 63) / 64) * 64;
-  const size_t shmem = (size_t)(W * 8 * RS + N) * sizeof(cplx) + (size_t)W * CPW * RAWC * 16;
-  int rc = dlpd_set_max_dyn_shared((const void*)k_zifft_filter<N, HP, MODE>, shmem);
+  typedef K3Lds<N, Cfg> Geo;
+  int rc = dlpd_set_max_dyn_shared((const void*)k_zifft_filter<N, HP, MODE>, Geo::BYTES);
   if (rc) return rc;
-  const int G = k3_group(CT, W * CPW, CPW > 1);   // channels per group (CPW per wave), <= W * CPW
+  const int G = k3_group(CT, Cfg::WC * Geo::CPW, Geo::CPW > 1);   // channels per group (CPW per wave), <= WC * CPW
   dim3 grid(N / Cfg::TY, N, nb), block(Cfg::NT);
-  DLPD_LAUNCH((k_zifft_filter<N, HP, MODE>), grid, block, shmem, st, Bw, out, CT, C, has_clash, G, W1t, b1, W2, b2,
+  DLPD_LAUNCH((k_zifft_filter<N, HP, MODE>), grid, block, Geo::BYTES, st, Bw, out, CT, C, has_clash, G, W1t, b1, W2, b2,
               has_clip, clip, thr, aux, cd);
   return dlpd_check_launch();
-}
-
-// fused K3 over several tiles per block (see k_zifft_filter_tiles)
-template <int N, int HP> static int launch_k3_tiles(const cplx* Bw, float* out, int CT, int C, int has_clash, int nb,
-                                                    const float* W1t, const float* b1, const float* W2, float b2,
-                                                    int has_clip, float clip, float thr, hipStream_t st, K3Aux aux,
-                                                    K3Cand cd) {
-  typedef K3Cfg<N, 1> Cfg;
-  constexpr int RS = N + 8, NZ = N / 2 + 1, W = Cfg::WC, NPAIR = Cfg::TY / 2, CPW = 8 / NPAIR;
-  constexpr int RAWC = ((NZ * NPAIR + 63) / 64) * 64;
-  const size_t shmem = (size_t)(W * 8 * RS + N) * sizeof(cplx) + (size_t)W * CPW * RAWC * 16;
-  int rc = dlpd_set_max_dyn_shared((const void*)k_zifft_filter_tiles<N, HP, 1>, shmem);
-  if (rc) return rc;
-  const int G = k3_group(CT, W * CPW, CPW > 1);
-  const int ntiles = (N / Cfg::TY) * N * nb, tpb = N / Cfg::TY;       // one x' plane per block
-  DLPD_LAUNCH((k_zifft_filter_tiles<N, HP, 1>), dim3((ntiles + tpb - 1) / tpb), dim3(Cfg::NT), shmem, st, Bw, out, CT, C,
-              has_clash, G, W1t, b1, W2, b2, has_clip, clip, thr, aux, ntiles, tpb, cd);
-  return dlpd_check_launch();
-}
-
-template <int N> static int k3_filter_dispatch(int HP, const cplx* Bw, float* V, int CT, int C, int has_clash, int nb,
-                                               const float* W1t, const float* b1, const float* W2, float b2,
-                                               int has_clip, float clip, float thr, hipStream_t st,
-                                               K3Aux aux = K3Aux{nullptr, 0, 0, 0},
-                                               K3Cand cd = K3Cand{nullptr, nullptr, nullptr, 0, 0}) {
-  if constexpr (N == 160) {                    // few groups per tile: the tile-walking kernel
-    switch (HP) {
-      case 2: return launch_k3_tiles<N, 2>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-      case 4: return launch_k3_tiles<N, 4>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-      case 8: return launch_k3_tiles<N, 8>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-      case 16: return launch_k3_tiles<N, 16>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-      case 24: return launch_k3_tiles<N, 24>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-      case 32: return launch_k3_tiles<N, 32>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-      default: return DLPD_ERR_UNSUPPORTED;
-    }
-  }
-  switch (HP) {
-    case 2: return launch_k3<N, 2, 1>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 4: return launch_k3<N, 4, 1>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 8: return launch_k3<N, 8, 1>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 16: return launch_k3<N, 16, 1>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 24: return launch_k3<N, 24, 1>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 32: return launch_k3<N, 32, 1>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
 }
 
 extern "C" {
@@ -1403,13 +1061,13 @@ int dlpd_debug_read_stamps(unsigned long long* host16) {
 #endif
 
 int dlpd_hidden_pad(int H) {
-  const int opts[6] = {2, 4, 8, 16, 24, 32};
-  for (int i = 0; i < 6; i++)
-    if (H <= opts[i]) return opts[i];
+  const int widths[] = {DLPD_HIDDEN_WIDTHS};
+  for (int w : widths)
+    if (H <= w) return w;
   return -1;
 }
 
-int dlpd_grid_supported(int L) { return (L == 32 || L == 40 || L == 64 || L == 80) ? 1 : 0; }
+int dlpd_grid_supported(int L) { return dlpd_listed<DLPD_BOXES>(L) ? 1 : 0; }
 
 // hidden width the FUSED pipeline pads H to on a fine grid of L^3 voxels per volume (two_res: plus a coarse grid of
 // (L/2)^3, the reference's layout): dlpd_hidden_pad's widths, and 48 -- the reference class default's hidden width,
@@ -1440,13 +1098,9 @@ int dlpd_zfft_oriented_ext(const float* vol, const float* R, void* wsA, int nb, 
   if (do_rotate && !R) return DLPD_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   cplx* A = (cplx*)wsA;
-  switch (L) {
-    case 32: return launch_k1<64>(vol, R, A, CT, nb, vol_bstride, do_rotate, center, st, CT_out, c_base, transposed, nullptr, extent);
-    case 40: return launch_k1<80>(vol, R, A, CT, nb, vol_bstride, do_rotate, center, st, CT_out, c_base, transposed, nullptr, extent);
-    case 64: return launch_k1<128>(vol, R, A, CT, nb, vol_bstride, do_rotate, center, st, CT_out, c_base, transposed, nullptr, extent);
-    case 80: return launch_k1<160>(vol, R, A, CT, nb, vol_bstride, do_rotate, center, st, CT_out, c_base, transposed, nullptr, extent);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    return launch_k1<2 * l()>(vol, R, A, CT, nb, vol_bstride, do_rotate, center, st, CT_out, c_base, transposed, nullptr, extent);
+  });
 }
 
 // given volumes (no rotation) with their occupancy maps: occ (nb, ceil(L/4)^3) bytes, one map per batch entry (all CT channels)
@@ -1455,13 +1109,9 @@ int dlpd_zfft_volumes_occ(const float* vol, const unsigned char* occ, void* wsA,
   if (!vol || !occ || !wsA || nb <= 0 || CT <= 0 || c_base < 0 || c_base + CT > CT_out) return DLPD_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   cplx* A = (cplx*)wsA;
-  switch (L) {
-    case 32: return launch_k1<64>(vol, nullptr, A, CT, nb, vol_bstride, 0, 0.f, st, CT_out, c_base, 0, nullptr, 0, occ, skip_empty);
-    case 40: return launch_k1<80>(vol, nullptr, A, CT, nb, vol_bstride, 0, 0.f, st, CT_out, c_base, 0, nullptr, 0, occ, skip_empty);
-    case 64: return launch_k1<128>(vol, nullptr, A, CT, nb, vol_bstride, 0, 0.f, st, CT_out, c_base, 0, nullptr, 0, occ, skip_empty);
-    case 80: return launch_k1<160>(vol, nullptr, A, CT, nb, vol_bstride, 0, 0.f, st, CT_out, c_base, 0, nullptr, 0, occ, skip_empty);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    return launch_k1<2 * l()>(vol, nullptr, A, CT, nb, vol_bstride, 0, 0.f, st, CT_out, c_base, 0, nullptr, 0, occ, skip_empty);
+  });
 }
 
 int dlpd_zfft_oriented(const float* vol, const float* R, void* wsA, int nb, int CT, int CT_out, int c_base, int L,
@@ -1488,13 +1138,9 @@ int dlpd_zfft_quads(const float* quads, const float* R, void* wsA, int nb, int C
   cplx* A = (cplx*)wsA;
   const float* dummy = quads;                          // the plain-volume pointer is unused on this path
   const float4* q4 = (const float4*)quads;
-  switch (L) {
-    case 32: return launch_k1<64>(dummy, R, A, CT, nb, 0, 1, center, st, CT_out, c_base, transposed, q4);
-    case 40: return launch_k1<80>(dummy, R, A, CT, nb, 0, 1, center, st, CT_out, c_base, transposed, q4);
-    case 64: return launch_k1<128>(dummy, R, A, CT, nb, 0, 1, center, st, CT_out, c_base, transposed, q4);
-    case 80: return launch_k1<160>(dummy, R, A, CT, nb, 0, 1, center, st, CT_out, c_base, transposed, q4);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    return launch_k1<2 * l()>(dummy, R, A, CT, nb, 0, 1, center, st, CT_out, c_base, transposed, q4);
+  });
 }
 
 size_t dlpd_channels_last_floats(int C, int L) {
@@ -1525,13 +1171,9 @@ int dlpd_zfft_channels_last_form(const float* cl, const float* R, void* wsA, int
   const float4* c4 = (const float4*)cl;
   if (form == 0) form = (L == 64 || L == 80) ? DLPD_K1_DEFAULT_FORM : 1;
   if (form == 2) return dlpd_k1_role_split(c4, R, A, C, nb, center, st, CT_out, c_base, extent, L);
-  switch (L) {
-    case 32: return launch_k1_cl<64>(c4, R, A, C, nb, center, st, CT_out, c_base, extent);
-    case 40: return launch_k1_cl<80>(c4, R, A, C, nb, center, st, CT_out, c_base, extent);
-    case 64: return launch_k1_cl<128>(c4, R, A, C, nb, center, st, CT_out, c_base, extent);
-    case 80: return launch_k1_cl<160>(c4, R, A, C, nb, center, st, CT_out, c_base, extent);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    return launch_k1_cl<2 * l()>(c4, R, A, C, nb, center, st, CT_out, c_base, extent);
+  });
 }
 
 // occ_src (ceil(L/4)^3 bytes: the stored ligand's cells, all channels) -> occ_out (nb maps): the cells of each ROTATED volume
@@ -1563,13 +1205,9 @@ int dlpd_zfft_channels_last_occ(const float* cl, const float* R, const unsigned 
   hipStream_t st = (hipStream_t)stream;
   cplx* A = (cplx*)wsA;
   const float4* c4 = (const float4*)cl;
-  switch (L) {
-    case 32: return launch_k1_cl<64>(c4, R, A, C, nb, center, st, CT_out, c_base, extent, occ, skip_empty);
-    case 40: return launch_k1_cl<80>(c4, R, A, C, nb, center, st, CT_out, c_base, extent, occ, skip_empty);
-    case 64: return launch_k1_cl<128>(c4, R, A, C, nb, center, st, CT_out, c_base, extent, occ, skip_empty);
-    case 80: return launch_k1_cl<160>(c4, R, A, C, nb, center, st, CT_out, c_base, extent, occ, skip_empty);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    return launch_k1_cl<2 * l()>(c4, R, A, C, nb, center, st, CT_out, c_base, extent, occ, skip_empty);
+  });
 }
 
 int dlpd_zfft_channels_last_ext(const float* cl, const float* R, void* wsA, int nb, int C, int CT_out, int c_base, int L,
@@ -1641,13 +1279,9 @@ int dlpd_zifft_real_part(const void* wsB, float* out, int nb, int CT, int nclip,
                          void* stream) {
   if (!wsB || !out || nb <= 0 || CT <= 0) return DLPD_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  switch (L) {
-    case 32: return launch_k3<64, 0, 0>((const cplx*)wsB, out, CT, nclip, 0, nb, nullptr, nullptr, nullptr, 0.f, has_clip, clip, 0.f, st);
-    case 40: return launch_k3<80, 0, 0>((const cplx*)wsB, out, CT, nclip, 0, nb, nullptr, nullptr, nullptr, 0.f, has_clip, clip, 0.f, st);
-    case 64: return launch_k3<128, 0, 0>((const cplx*)wsB, out, CT, nclip, 0, nb, nullptr, nullptr, nullptr, 0.f, has_clip, clip, 0.f, st);
-    case 80: return launch_k3<160, 0, 0>((const cplx*)wsB, out, CT, nclip, 0, nb, nullptr, nullptr, nullptr, 0.f, has_clip, clip, 0.f, st);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    return launch_k3<2 * l(), 0, 0>((const cplx*)wsB, out, CT, nclip, 0, nb, nullptr, nullptr, nullptr, 0.f, has_clip, clip, 0.f, st);
+  });
 }
 
 // wsB (nb, C, NZ, N, N) -> pre (nb, HP, N^3) = b1 + W1rows^T clamp(correlations): z C2R fused with the (linear) first
@@ -1665,20 +1299,12 @@ int dlpd_zifft_preact_form(const void* wsB, float* pre, int nb, int C, int L, co
   const cplx* B = (const cplx*)wsB;
   if (form == 0) form = DLPD_K3_DEFAULT_FORM;
   if (form == 2 && dlpd_k3r_supported(L, HP, 2)) return dlpd_k3r_preact(B, pre, C, nb, L, W1rows, HP, b1, has_clip, clip, st);
-#define DLPD_ZP(NN, H) case H: return launch_k3<NN, H, 2>(B, pre, C, C, 0, nb, W1rows, b1, b1, 0.f, has_clip, clip, 0.f, st)
-#define DLPD_ZPN(NN) switch (HP) { DLPD_ZP(NN, 2); DLPD_ZP(NN, 4); DLPD_ZP(NN, 8); DLPD_ZP(NN, 16); DLPD_ZP(NN, 24); DLPD_ZP(NN, 32); \
-                                   default: return DLPD_ERR_UNSUPPORTED; }
-  switch (L) {
-    case 32: DLPD_ZPN(64)
-#ifdef DLPD_TEST_VARIANTS
-    case 40: DLPD_ZPN(80)                      // (product: the role-split kernel above; coarse grids of 64 / 80 have no fine grid)
-    case 64: DLPD_ZPN(128)
-    case 80: DLPD_ZPN(160)
-#endif
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
-#undef DLPD_ZPN
-#undef DLPD_ZP
+  return dlpd_dispatch<DLPD_K3_MODE2_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    return dlpd_dispatch<DLPD_HIDDEN_WIDTHS>(HP, [&](auto h) {
+      return launch_k3<N, h(), 2>(B, pre, C, C, 0, nb, W1rows, b1, b1, 0.f, has_clip, clip, 0.f, st);
+    });
+  });
 }
 
 int dlpd_zifft_real(const void* wsB, float* out, int nb, int CT, int L, int has_clip, float clip, void* stream) {
@@ -1714,7 +1340,7 @@ int dlpd_zifft_filter_cand(const void* wsB, float* V, int nb, int C, int has_cla
 }
 
 // The same with the kernel formulation named: form 0 = the library's default, 1 = channel-owning waves with
-// barrier-separated transform / filter phases (k_zifft_filter[_tiles]), 2 = role-split transform / filter waves
+// barrier-separated transform / filter phases (k_zifft_filter), 2 = role-split transform / filter waves
 // (dlpd_k3r.hip; falls back to 1 where it is not compiled).  Same arithmetic, same results bit for bit.
 int dlpd_zifft_filter_form(const void* wsB, float* V, int nb, int C, int has_clash, int L, const float* W1t,
                            const float* b1, const float* W2, float b2, int HP, int has_clip, float clip, float thr,
@@ -1730,17 +1356,12 @@ int dlpd_zifft_filter_form(const void* wsB, float* V, int nb, int C, int has_cla
   if (form == 0) form = DLPD_K3_DEFAULT_FORM;
   if (form == 2 && dlpd_k3r_supported(L, HP, 1) && (Caux == 0 || aux_is_preact))
     return dlpd_k3r_filter((const cplx*)wsB, V, CT, C, has_clash, nb, L, W1t, HP, b1, W2, b2, has_clip, clip, thr, ax, cd, st);
-  switch (L) {
-    case 32: return k3_filter_dispatch<64>(HP, (const cplx*)wsB, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, ax, cd);
-    case 40: return k3_filter_dispatch<80>(HP, (const cplx*)wsB, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, ax, cd);
-#ifdef DLPD_TEST_VARIANTS
-    // the channel-owning formulation at N = 128 / 160: no default path reaches it (the role-split kernel covers every
-    // hidden width it has), it is the bit-exactness reference of the tests -- compiled into tests/variants only
-    case 64: return k3_filter_dispatch<128>(HP, (const cplx*)wsB, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, ax, cd);
-    case 80: return k3_filter_dispatch<160>(HP, (const cplx*)wsB, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, ax, cd);
-#endif
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_K3_FORM1_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    return dlpd_dispatch<DLPD_HIDDEN_WIDTHS>(HP, [&](auto h) {
+      return launch_k3<N, h(), 1>((const cplx*)wsB, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, ax, cd);
+    });
+  });
 }
 
 int dlpd_zifft_filter(const void* wsB, float* V, int nb, int C, int has_clash, int L, const float* W1t,
@@ -1786,13 +1407,10 @@ int dlpd_filter_preact(const float* conv1, int C1, int N1, const float* W1rows, 
   const size_t n = (size_t)N1 * N1 * N1;
   size_t nblk = ((size_t)nb * n / 4 + 255) / 256;
   if (nblk > 65536) nblk = 65536;
-#define DLPD_FP(H) case H: DLPD_LAUNCH((k_filter_preact<H>), dim3((unsigned)nblk), dim3(256), 0, st, conv1, C1, n, \
-                                       W1rows, b1, pre, nb); return dlpd_check_launch()
-  switch (HP) {
-    DLPD_FP(2); DLPD_FP(4); DLPD_FP(8); DLPD_FP(16); DLPD_FP(24); DLPD_FP(32);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
-#undef DLPD_FP
+  return dlpd_dispatch<DLPD_HIDDEN_WIDTHS>(HP, [&](auto h) {
+    DLPD_LAUNCH((k_filter_preact<h()>), dim3((unsigned)nblk), dim3(256), 0, st, conv1, C1, n, W1rows, b1, pre, nb);
+    return dlpd_check_launch();
+  });
 }
 
 int dlpd_filter_volumes(const float* conv0, int C0, long long conv0_bstride, int N0, const float* conv1, int C1,
@@ -1804,13 +1422,10 @@ int dlpd_filter_volumes(const float* conv0, int C0, long long conv0_bstride, int
   if (conv1_is_preact && (C1 <= 0 || N0 / N1 > 2)) return DLPD_ERR_ARG;
   if (has_clash && !mask_norm) return DLPD_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-#define DLPD_FV(H) case H: return launch_filter_vec<H>(conv0, C0, conv0_bstride, N0, conv1, C1, N1, conv1_is_preact, mask_norm, \
-                                                      mask_bstride, thr, has_clash, W1t, b1, W2, b2, V, nb, st)
-  switch (HP) {
-    DLPD_FV(2); DLPD_FV(4); DLPD_FV(8); DLPD_FV(16); DLPD_FV(24); DLPD_FV(32);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
-#undef DLPD_FV
+  return dlpd_dispatch<DLPD_HIDDEN_WIDTHS>(HP, [&](auto h) {
+    return launch_filter_vec<h()>(conv0, C0, conv0_bstride, N0, conv1, C1, N1, conv1_is_preact, mask_norm, mask_bstride, thr,
+                                  has_clash, W1t, b1, W2, b2, V, nb, st);
+  });
 }
 
 // Generic per-voxel filter over real correlation volumes (multi-resolution model).

@@ -54,6 +54,15 @@ template <int DIR> DLPD_HD cplx c_rotcs(cplx a, float c, float s) {
 }
 #endif
 
+// tw[k] = exp(-2 pi i k / N), k < N, made by the block's nthreads threads (every kernel's twiddle table in LDS)
+template <int N> DLPD_D void init_twiddles(cplx* tw, int tid, int nthreads) {
+  for (int k = tid; k < N; k += nthreads) {
+    double s, c;
+    sincospi(-2.0 * (double)k / (double)N, &s, &c);
+    tw[k] = c_make((float)c, (float)s);
+  }
+}
+
 #define DLPD_SQRT1_2 0.70710678118654752440f
 #define DLPD_COS_PI_8 0.92387953251128675613f
 #define DLPD_SIN_PI_8 0.38268343236508977173f

@@ -2,12 +2,29 @@
 #pragma once
 #include <dlpd_platform.h>
 #include <stdio.h>
+#include <type_traits>
 
 #define DLPD_OK 0
 #define DLPD_ERR_ARG 1          // null pointer / non-positive size
 #define DLPD_ERR_UNSUPPORTED 2  // grid size / hidden width / K outside the compiled set
 #define DLPD_ERR_LAUNCH 3       // HIP reported a launch error
 #define DLPD_MAX_HIDDEN 64
+// Boxes L (grid N = 2L) the FFT pipeline is compiled for
+#define DLPD_BOXES 32, 40, 64, 80
+// Hidden widths the filter kernels are compiled for (dlpd_hidden_pad rounds H up to one of them; 96 accumulators per thread
+// are 4 voxels x <= 24..32), and those of the role-split K3, which adds 48 on two voxels per thread (dlpd_k3r.hip, WIDE)
+#define DLPD_HIDDEN_WIDTHS 2, 4, 8, 16, 24, 32
+#define DLPD_HIDDEN_WIDTHS_RS DLPD_HIDDEN_WIDTHS, 48
+
+// Run-time value -> template argument (host only): f is called with std::integral_constant<int, V> for the V of the list that
+// equals v -- dlpd_dispatch<32, 40, 64, 80>(L, [&](auto l) { return launch<2 * l()>(...); }) -- and its status returned; a
+// value outside the list is DLPD_ERR_UNSUPPORTED and calls nothing.
+template <int... Vs, class F> static inline int dlpd_dispatch(int v, F&& f) {
+  int rc = DLPD_ERR_UNSUPPORTED;
+  (void)(... || (v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)));
+  return rc;
+}
+template <int... Vs> static inline bool dlpd_listed(int v) { return (... || (v == Vs)); }
 
 // hipGetLastError() is sticky per thread and also reports benign codes left behind by the
 // caller's own runtime use (e.g. torch's event queries): clear it before each launch, latch a

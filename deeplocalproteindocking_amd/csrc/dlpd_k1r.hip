@@ -41,9 +41,10 @@ extern "C" int dlpd_k1_form_supported(int L, int form) {
   return (form == 0 || form == 1) ? dlpd_grid_supported(L) : 0;
 }
 #else
+#define DLPD_K1R_BOXES 64, 80
 extern "C" int dlpd_k1_form_supported(int L, int form) {
   if (form == 0 || form == 1) return dlpd_grid_supported(L);
-  return (form == 2 && (L == 64 || L == 80)) ? 1 : 0;
+  return (form == 2 && dlpd_listed<DLPD_K1R_BOXES>(L)) ? 1 : 0;
 }
 
 template <int N> struct K1RsCfg {
@@ -131,11 +132,7 @@ k_rotate_zfft_cl_rs(const float4* __restrict__ cl, const float* __restrict__ R, 
   const int total = gper * per;
   const int n_items = min(items_per_block, total - first);
   if (n_items <= 0) return;
-  for (int k = tid; k < N; k += G::NT) {                // the table of k_rotate_zfft_cl (init_twiddles, dlpd_corr.hip)
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)N, &s, &c);
-    tw[k] = c_make((float)c, (float)s);
-  }
+  init_twiddles<N>(tw, tid, G::NT);
   DLPD_STAMP_DECL;
 
   // ---- gather role: item `it` into input buffer `buf`
@@ -287,10 +284,8 @@ template <int N> static int launch_k1_rs(const float4* cl, const float* R, cplx*
 
 int dlpd_k1_role_split(const float4* cl, const float* R, cplx* A, int C, int nb, float c0, hipStream_t st, int CT_out, int c_base,
                        int ext, int L) {
-  switch (L) {
-    case 64: return launch_k1_rs<128>(cl, R, A, C, nb, c0, st, CT_out, c_base, ext);
-    case 80: return launch_k1_rs<160>(cl, R, A, C, nb, c0, st, CT_out, c_base, ext);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_K1R_BOXES>(L, [&](auto l) {
+    return launch_k1_rs<2 * l()>(cl, R, A, C, nb, c0, st, CT_out, c_base, ext);
+  });
 }
 #endif  // DLPD_TEST_VARIANTS

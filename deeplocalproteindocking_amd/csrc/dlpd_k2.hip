@@ -7,14 +7,6 @@
 #include "dlpd_fft.h"
 #include "dlpd_internal.h"
 
-template <int N> DLPD_D void init_twiddles(cplx* tw, int tid, int nthreads) {
-  for (int k = tid; k < N; k += nthreads) {
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)N, &s, &c);
-    tw[k] = c_make((float)c, (float)s);
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // K2: one block per (c, kz), looping over the nb rotations of the batch (persistent over b).
 //   1-D grid NZ*CT*nsplit, block 4N threads (W = N/16 waves), dynamic LDS N*(N+8)*8 B (one swizzled N x N slab).
@@ -732,13 +724,11 @@ template <int N, int WV> static int launch_k2_quad(const cplx* A, const cplx* re
 }
 
 int dlpd_k2_forward(const cplx* A, cplx* out, int CT, int nb, int L, float scale, hipStream_t st) {
-  switch (L) {
-    case 32: return launch_k2<64, 0>(A, nullptr, out, CT, nb, 0, scale, st);
-    case 40: return launch_k2<80, 0>(A, nullptr, out, CT, nb, 0, scale, st);
-    case 64: return launch_k2<128, 0>(A, nullptr, out, CT, nb, 0, scale, st);
-    case 80: return launch_k2_split<160, 0>(A, nullptr, out, CT, nb, 0, scale, st);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    if constexpr (N == 160) return launch_k2_split<N, 0>(A, nullptr, out, CT, nb, 0, scale, st);
+    else return launch_k2<N, 0>(A, nullptr, out, CT, nb, 0, scale, st);
+  });
 }
 
 // N = 160 with 4-lane pencils and affine LDS addressing: dlpd_k2q.hip (untransposed slabs)
@@ -752,19 +742,24 @@ int dlpd_k2q_pack_receptor(const cplx* rec, void* packed, int CT, int L, hipStre
 #define DLPD_K2_S4 1
 #endif
 
+// Slabs that K1 stored transposed (dlpd_zfft_oriented, the per-channel K1 of ligands with fewer than 8 channels): every
+// compiled grid except N = 160, whose transposed reader is round 2's quad kernel -- kept as a TEST VARIANT
+// (-DDLPD_TEST_VARIANTS: tests/variants, never in libdlpd.so); the engine asks and visits box 80 in one orientation.
+#ifdef DLPD_TEST_VARIANTS
+#define DLPD_K2_ORIENTED_BOXES DLPD_BOXES
+#else
+#define DLPD_K2_ORIENTED_BOXES 32, 40, 64
+#endif
+
 int dlpd_k2_correlate(const cplx* A, const cplx* rec, cplx* out, int CT, int nb, int L, long long rbs, hipStream_t st,
                       int transposed) {
   if (((DLPD_K2_Q4 && L == 80) || (DLPD_K2_S4 && L == 40)) && !transposed)
     return dlpd_k2q_correlate(A, rec, out, CT, nb, L, rbs, k2_nsplit_override(), st, 0);
-  switch (L) {
-    case 32: return launch_k2<64, 1>(A, rec, out, CT, nb, rbs, 1.f, st, transposed);
-    case 40: return launch_k2<80, 1>(A, rec, out, CT, nb, rbs, 1.f, st, transposed);
-    case 64: return launch_k2<128, 1>(A, rec, out, CT, nb, rbs, 1.f, st, transposed);
-#ifdef DLPD_TEST_VARIANTS
-    case 80: return launch_k2_quad<160, DLPD_K2Q_WAVES>(A, rec, out, CT, nb, rbs, st, transposed);
-#endif
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_K2_ORIENTED_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    if constexpr (N == 160) return launch_k2_quad<N, DLPD_K2Q_WAVES>(A, rec, out, CT, nb, rbs, st, transposed);
+    else return launch_k2<N, 1>(A, rec, out, CT, nb, rbs, 1.f, st, transposed);
+  });
 }
 
 // The receptor spectrum re-ordered for the grids whose K2 re-reads it for every rotation (the 4-lane-pencil kernels of
@@ -783,13 +778,4 @@ int dlpd_k2_correlate_packed(const cplx* A, const cplx* packed, cplx* out, int C
   return dlpd_k2q_correlate(A, packed, out, CT, nb, L, 0, k2_nsplit_override(), st, 1, pmap, nmasked);
 }
 
-// Slabs that K1 stored transposed (dlpd_zfft_oriented, the per-channel K1 of ligands with fewer than 8 channels): every
-// compiled grid except N = 160, whose transposed reader is round 2's quad kernel -- kept as a TEST VARIANT
-// (-DDLPD_TEST_VARIANTS: tests/variants, never in libdlpd.so); the engine asks and visits box 80 in one orientation.
-int dlpd_k2_orientation_supported(int L) {
-#ifdef DLPD_TEST_VARIANTS
-  return (L == 32 || L == 40 || L == 64 || L == 80) ? 1 : 0;
-#else
-  return (L == 32 || L == 40 || L == 64) ? 1 : 0;
-#endif
-}
+int dlpd_k2_orientation_supported(int L) { return dlpd_listed<DLPD_K2_ORIENTED_BOXES>(L) ? 1 : 0; }

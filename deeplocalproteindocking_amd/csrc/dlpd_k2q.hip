@@ -44,14 +44,6 @@
 #ifndef DLPD_K2Q_H0_REGS
 #define DLPD_K2Q_H0_REGS 3                   // pairs of H_0 kept in registers (of 5); the rest waits in LDS
 #endif
-template <int N> DLPD_D void init_twiddles_k2q(cplx* tw, int tid, int nthreads) {
-  for (int k = tid; k < N; k += nthreads) {
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)N, &s, &c);
-    tw[k] = c_make((float)c, (float)s);
-  }
-}
-
 #ifdef DLPD_STAMPS
 __device__ unsigned long long dlpd_stamps_k2q[16];
 extern "C" int dlpd_debug_read_stamps_k2q(unsigned long long* host16) {
@@ -210,8 +202,8 @@ k_xy_corr_q4(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __r
   if (b_beg >= b_end) return;
   cplx* tw = S + 2 * SUB;                              // exp(-2 pi i k / N)
   cplx* twh = tw + N;                                  // exp(-2 pi i k / H)
-  init_twiddles_k2q<N>(tw, tid, NT);
-  init_twiddles_k2q<H>(twh, tid, NT);
+  init_twiddles<N>(tw, tid, NT);
+  init_twiddles<H>(twh, tid, NT);
 
   const int t = lane & 3, pidx = lane >> 2;            // thread of the pencil, pencil of the set
   // row set: rows 8w..8w+7 of sub-slab 0 (lanes 0-31) and of sub-slab 1 (lanes 32-63)
@@ -439,7 +431,7 @@ k_xy_corr_s4(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __r
   const int b_beg = (int)(((long long)nb * part) / nsplit), b_end = (int)(((long long)nb * (part + 1)) / nsplit);
   if (b_beg >= b_end) return;
   cplx* twh = S + HR * RS;                             // exp(-2 pi i k / N)
-  init_twiddles_k2q<N>(twh, tid, NT);
+  init_twiddles<N>(twh, tid, NT);
   const int t = lane & 3, pidx = lane >> 2;
   // forward rows: lanes 0-31 the wave's 8 input rows, lanes 32-63 dummy rows 40 + 8w..
   const int fbase = ((pidx >> 3) * L + 8 * wave + (pidx & 7)) * RS;

@@ -4,8 +4,8 @@
 //   src/Models/DockingModels.py:70-83   per-channel correlation (its z-inverse), upsample + concat, SimpleFilter MLP
 //   src/Docker/Docker.py:226,232        clash threshold, mask multiply
 //
-// Same inputs, outputs and arithmetic (same products, same summation order) as k_zifft_filter /
-// k_zifft_filter_tiles of dlpd_corr.hip.  There EVERY wave alternates between the two halves of the work -- pack +
+// Same inputs, outputs and arithmetic (same products, same summation order) as k_zifft_filter of
+// dlpd_corr.hip.  There EVERY wave alternates between the two halves of the work -- pack +
 // wave-local z transform of "its" channel (LDS-bound), then, behind a block barrier, the first-layer multiply-adds of
 // its voxels over all channels of the group (VALU-bound) -- so the LDS pipe idles while the vector units work and
 // vice versa (rocprofv3, round 2: SQ_WAIT_ANY 30 % of the wave cycles at N = 128, 53 % at N = 160, where in addition
@@ -42,14 +42,6 @@
 #include "dlpd_fft.h"
 #include "dlpd_internal.h"
 #include "dlpd_k3.h"
-
-template <int N> DLPD_D void init_twiddles_k3r(cplx* tw, int tid, int nthreads) {
-  for (int k = tid; k < N; k += nthreads) {
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)N, &s, &c);
-    tw[k] = c_make((float)c, (float)s);
-  }
-}
 
 // F transform waves, M filter waves, TY rows per tile (16: a transform wave owns one channel = 8 two-row pencils;
 // 8: two channels of 4 pencils -- 64-byte DMA runs: only where two voxels per filter thread leave no room for 16 rows),
@@ -268,9 +260,10 @@ k_zifft_filter_rs(const cplx* __restrict__ Bw, float* __restrict__ out, int CT, 
                   float b2, int has_clip, float clip, float thr, K3Aux aux, int ntiles, int tpb, K3Cand cd) {
   typedef K3rCfg<N, (HP > K3rWideAbove<N>::value)> Cfg;
   constexpr int F = Cfg::F, M = Cfg::M, TY = Cfg::TY, RAWBUF = Cfg::RAWBUF;
-  constexpr int NZ = N / 2 + 1, RS = N + 8, NPAIR = TY / 2, NYT = N / TY;
-  constexpr int CPW = 8 / NPAIR;               // channels per transform wave: its 8 pencils = CPW channels x NPAIR row pairs
-  constexpr int LPK = 64 / NPAIR;              // kz rows per 64-lane DMA instruction
+  typedef K3rLds<N, Cfg> Geo;                  // (dlpd_k3.h: shared with launch_k3r)
+  constexpr int NZ = Geo::NZ, RS = Geo::RS, NPAIR = Geo::NPAIR, NYT = N / TY;
+  constexpr int CPW = Geo::CPW;                // channels per transform wave: its 8 pencils = CPW channels x NPAIR row pairs
+  constexpr int LPK = Geo::LPK;                // kz rows per 64-lane DMA instruction
   constexpr int NFULL = (N / 2) / LPK;         // full 64-lane DMA instructions per channel (bins 0..N/2-1)
   constexpr int GMAX = F * CPW;                // channel slots per group
   constexpr int NTM = 64 * M;                  // filter threads
@@ -278,9 +271,7 @@ k_zifft_filter_rs(const cplx* __restrict__ Bw, float* __restrict__ out, int CT, 
   constexpr int MSTEP = NTM / N;               // pair stride between a thread's values
   constexpr int PBUF = Cfg::PBUF;              // pencil buffers (2: see "TWO PENCIL BUFFERS" below)
   constexpr int PSZ = F * 8 * RS;              // complex elements per pencil buffer
-  // float4 slots per raw channel: whole waves, or -- where two pencil buffers leave no room -- exactly the channel, the last
-  // DMA instruction then running on NPAIR lanes only
-  constexpr int RAWC = (PBUF == 2) ? NZ * NPAIR : ((NZ * NPAIR + 63) / 64) * 64;
+  constexpr int RAWC = Geo::RAWC;              // float4 slots per raw channel
   static_assert(NPAIR == 8 || NPAIR == 4, "one transform wave = 8 pencils x 8 threads");
   static_assert(EPT >= 1 && EPT * NTM == NPAIR * N && NTM % N == 0, "the filter waves tile the voxels exactly");
   static_assert(NZ * NPAIR == NFULL * 64 + NPAIR, "raw channel = NFULL full DMA instructions + one short one");
@@ -317,7 +308,7 @@ k_zifft_filter_rs(const cplx* __restrict__ Bw, float* __restrict__ out, int CT, 
   if (t_beg >= t_end) return;
   // a block's tiles lie in ONE x' plane (tpb divides the NYT tiles of a plane): plane, x' and rotation are decoded once
   const int plane = t_beg / NYT, plane_x = plane % N, plane_b = plane / N;
-  init_twiddles_k3r<N>(tw, tid, 64 * (F + M));
+  init_twiddles<N>(tw, tid, 64 * (F + M));
   const unsigned cand_tau = (MODE == 1 && cd.keys) ? *cd.tau : 0u;
   // no clip = a clamp to +-infinity, which returns its argument: one v_med3 per value instead of a v_med3 and a select
   const float clampv = has_clip ? clip : __builtin_inff();
@@ -649,64 +640,41 @@ k_zifft_filter_rs(const cplx* __restrict__ Bw, float* __restrict__ out, int CT, 
 #ifndef DLPD_K3R_TPB_DIV
 #define DLPD_K3R_TPB_DIV 1                   // tiles per block = (y-tiles of an x' plane) / DIV
 #endif
-static int k3r_group(int CT, int maxg, bool balanced) {
-  if (!balanced) return CT < maxg ? CT : maxg;
-  const int ng = (CT + maxg - 1) / maxg;
-  return (CT + ng - 1) / ng;
-}
-
-#ifndef DLPD_K3R_TPB_DIV
-#define DLPD_K3R_TPB_DIV 1                   // tiles per block = (y-tiles of an x' plane) / DIV
-#endif
 template <int N, int HP, int MODE> static int launch_k3r(const cplx* Bw, float* out, int CT, int C, int has_clash, int nb,
                                                          const float* W1t, const float* b1, const float* W2, float b2,
                                                          int has_clip, float clip, float thr, hipStream_t st, K3Aux aux,
                                                          K3Cand cd) {
   typedef K3rCfg<N, (HP > K3rWideAbove<N>::value)> Cfg;
-  constexpr int RS = N + 8, NZ = N / 2 + 1, NPAIR = Cfg::TY / 2, CPW = 8 / NPAIR;
-  constexpr int RAWC = (Cfg::PBUF == 2) ? NZ * NPAIR : ((NZ * NPAIR + 63) / 64) * 64;
-  const size_t shmem = (size_t)(Cfg::PBUF * Cfg::F * 8 * RS + N) * sizeof(cplx) + (size_t)Cfg::RAWBUF * Cfg::F * CPW * RAWC * 16;
-  int rc = dlpd_set_max_dyn_shared((const void*)k_zifft_filter_rs<N, HP, MODE>, shmem);
+  typedef K3rLds<N, Cfg> Geo;
+  int rc = dlpd_set_max_dyn_shared((const void*)k_zifft_filter_rs<N, HP, MODE>, Geo::BYTES);
   if (rc) return rc;
-  const int G = k3r_group(CT, Cfg::F * CPW, true);
+  const int G = k3_group(CT, Cfg::F * Geo::CPW, true);
   const int ntiles = (N / Cfg::TY) * N * nb, tpb = (N / Cfg::TY) / DLPD_K3R_TPB_DIV;
-  DLPD_LAUNCH((k_zifft_filter_rs<N, HP, MODE>), dim3((ntiles + tpb - 1) / tpb), dim3(64 * (Cfg::F + Cfg::M)), shmem, st, Bw,
+  DLPD_LAUNCH((k_zifft_filter_rs<N, HP, MODE>), dim3((ntiles + tpb - 1) / tpb), dim3(64 * (Cfg::F + Cfg::M)), Geo::BYTES, st, Bw,
               out, CT, C, has_clash, G, W1t, b1, W2, b2, has_clip, clip, thr, aux, ntiles, tpb, cd);
   return dlpd_check_launch();
 }
 
-// hidden widths the role-split kernel is compiled for (96 accumulators: 4 voxels x <= 24..32, or 2 voxels x 48)
+// where the role-split kernel is compiled: the filter (mode 1) at boxes 64 / 80, the coarse pre-activations (mode 2) at box 40
+#define DLPD_K3R_FILTER_BOXES 64, 80
+#define DLPD_K3R_PREACT_BOXES 40
 int dlpd_k3r_supported(int L, int HP, int mode) {
-  if (HP != 2 && HP != 4 && HP != 8 && HP != 16 && HP != 24 && HP != 32 && HP != 48) return 0;
-  if (mode == 1) return (L == 64 || L == 80) ? 1 : 0;
-  if (mode == 2) return (L == 40) ? 1 : 0;
+  if (!dlpd_listed<DLPD_HIDDEN_WIDTHS_RS>(HP)) return 0;
+  if (mode == 1) return dlpd_listed<DLPD_K3R_FILTER_BOXES>(L) ? 1 : 0;
+  if (mode == 2) return dlpd_listed<DLPD_K3R_PREACT_BOXES>(L) ? 1 : 0;
   return 0;
-}
-
-template <int N, int MODE> static int k3r_dispatch(int HP, const cplx* Bw, float* out, int CT, int C, int has_clash, int nb,
-                                                   const float* W1t, const float* b1, const float* W2, float b2,
-                                                   int has_clip, float clip, float thr, hipStream_t st, K3Aux aux, K3Cand cd) {
-  switch (HP) {
-    case 2: return launch_k3r<N, 2, MODE>(Bw, out, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 4: return launch_k3r<N, 4, MODE>(Bw, out, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 8: return launch_k3r<N, 8, MODE>(Bw, out, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 16: return launch_k3r<N, 16, MODE>(Bw, out, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 24: return launch_k3r<N, 24, MODE>(Bw, out, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 32: return launch_k3r<N, 32, MODE>(Bw, out, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 48: return launch_k3r<N, 48, MODE>(Bw, out, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
 }
 
 // wsB -> V (nb, N^3); aux: HP pre-activation planes of the coarse grid (is_preact) or none
 int dlpd_k3r_filter(const cplx* Bw, float* V, int CT, int C, int has_clash, int nb, int L, const float* W1t, int HP,
                     const float* b1, const float* W2, float b2, int has_clip, float clip, float thr, K3Aux aux, K3Cand cd,
                     hipStream_t st) {
-  switch (L) {
-    case 64: return k3r_dispatch<128, 1>(HP, Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    case 80: return k3r_dispatch<160, 1>(HP, Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_K3R_FILTER_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    return dlpd_dispatch<DLPD_HIDDEN_WIDTHS_RS>(HP, [&](auto h) {
+      return launch_k3r<N, h(), 1>(Bw, V, CT, C, has_clash, nb, W1t, b1, W2, b2, has_clip, clip, thr, st, aux, cd);
+    });
+  });
 }
 
 // wsB (nb, C, NZ, N, N) -> pre (nb, HP, N^3): z C2R fused with the (linear) first layer over these C channels
@@ -714,8 +682,10 @@ int dlpd_k3r_preact(const cplx* Bw, float* pre, int C, int nb, int L, const floa
                     int has_clip, float clip, hipStream_t st) {
   const K3Aux ax = {nullptr, 0, 0, 0};
   const K3Cand cd = {nullptr, nullptr, nullptr, 0, 0};
-  switch (L) {
-    case 40: return k3r_dispatch<80, 2>(HP, Bw, pre, C, C, 0, nb, W1rows, b1, b1, 0.f, has_clip, clip, 0.f, st, ax, cd);
-    default: return DLPD_ERR_UNSUPPORTED;
-  }
+  return dlpd_dispatch<DLPD_K3R_PREACT_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    return dlpd_dispatch<DLPD_HIDDEN_WIDTHS_RS>(HP, [&](auto h) {
+      return launch_k3r<N, h(), 2>(Bw, pre, C, C, 0, nb, W1rows, b1, b1, 0.f, has_clip, clip, 0.f, st, ax, cd);
+    });
+  });
 }

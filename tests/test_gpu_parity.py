@@ -1134,8 +1134,8 @@ def test_scores_do_not_change_beside_the_plugin_and_the_radix_select(dev, co_run
 
 
 def test_k3_role_split_equals_the_channel_owning_k3(dev, variants):
-    """k_zifft_filter_rs (dedicated transform / filter waves, the default) bit for bit against k_zifft_filter[_tiles]
-    (every wave owns a channel) and against the oracle: 48 channels x 64^3 (13 groups of 4, the last one the clash
+    """k_zifft_filter_rs (dedicated transform / filter waves, the default) bit for bit against k_zifft_filter
+    (every wave owns a channel; one tile per block at every box) and against the oracle: 48 channels x 64^3 (13 groups of 4, the last one the clash
     channel alone), the reference's real shapes [16 @ 80^3, 32 @ 40^3] with the coarse pre-activation planes through
     both forms, and 48 channels x 80^3 (five groups of ten)."""
     from test_kernels_emu import _k3_both_formulations
@@ -1149,6 +1149,82 @@ def test_k3_role_split_equals_the_channel_owning_k3(dev, variants):
     eng.set_ligand(torch.zeros(2, 64, 64, 64), torch.zeros(64, 64, 64))
     with pytest.raises(RuntimeError, match="UNSUPPORTED"):
         eng.score_batch(torch.eye(3, device=dev).reshape(1, 3, 3).contiguous())
+
+
+@pytest.mark.parametrize("C,seed,C1,nb", [(10, 11, 0, 1), (6, 5, 4, 2)])
+def test_k3_both_formulations_at_box_80_small_shapes(dev, variants, C, seed, C1, nb):
+    """The channel-owning K3 at N = 160 (8-row tiles, two channels per wave, one tile per block) against the role-split kernel,
+    bit for bit, and the oracle, on shapes that do not fill the groups: 10 + clash = 11 channels are two balanced groups of
+    6 + 5 (one wave carries a single channel, the clash channel closes the second group); 6 + clash = 7 channels are one group,
+    with 4 coarse channels whose pre-activation planes go through both forms at box 40, two batch entries.  Hidden width 20
+    (padded to 24), clip biting."""
+    from test_kernels_emu import _k3_both_formulations
+    _k3_both_formulations(variants, dev, 80, C, 20, 0.4, seed, C1=C1, nb=nb)
+
+
+def test_candidate_lists_through_the_channel_owning_k3_at_box_80(dev, variants):
+    """search() with K3's candidate lists (k3_emit) through form 1 and form 2 at N = 160: the scores are the same bits, so the
+    ranked lists must be the same entries."""
+    from deeplocalproteindocking_amd.engine import DockingEngine
+    L, C, H = 80, 6, 20
+    g = torch.Generator().manual_seed(21)
+    rec, lig = torch.randn(C, L, L, L, generator=g) * 0.05, torch.randn(C, L, L, L, generator=g) * 0.05
+    recf, ligf = torch.rand(L, L, L, generator=g), torch.rand(L, L, L, generator=g)
+    W1, b1 = torch.randn(H, C, generator=g) * 0.4, torch.randn(H, generator=g) * 0.1
+    W2, b2 = torch.randn(1, H, generator=g), torch.randn(1, generator=g)
+    R = _rots(6, seed=21)
+    got = {}
+    for form in (1, 2):
+        eng = DockingEngine(L, C, W1, b1, W2, b2, clip=0.4, threshold_clash=0.125 * L ** 3, max_conf=16, batch=2, device=dev,
+                            lib=variants, k3_form=form)
+        assert eng.prefilter                                       # the candidate path is what is under test
+        eng.set_receptor(rec, recf)
+        eng.set_ligand(lig, ligf)
+        eng.reset_top()
+        eng.search(R)
+        got[form] = eng.top_entries()
+        assert 0 < int(eng.top.tau[0].item()) < 0x80000000         # a negative K-th score was published: the lists were live
+    assert len(got[1][0]) == 16
+    for a, b in zip(got[1], got[2]):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("H", [2, 4, 8, 16, 24, 32])
+@pytest.mark.parametrize("L", [32, 64])
+def test_k3_every_hidden_width_of_the_dispatch_table(dev, variants, L, H):
+    """Every row of the hidden-width table of dlpd_zifft_filter_form at boxes 32 (one formulation: both requests take it) and
+    64 (channel-owning against role-split), 3 score channels + clash."""
+    from test_kernels_emu import _k3_both_formulations
+    _k3_both_formulations(variants, dev, L, 3, H, 0.4, 100 + H)
+
+
+@pytest.mark.parametrize("H", [8, 5])
+def test_filter_volumes_padded_and_generic_widths(dev, H):
+    """ops.filter_volumes on materialised volumes: H = 8 is a compiled width (the vectorised kernel), H = 5 is not (the generic
+    kernel).  Against the float64 MLP; bound: the contract band, 1e-4 of max|V| (float32 chains of 3 + H terms are far inside)."""
+    from deeplocalproteindocking_amd.ops import filter_volumes
+    g = torch.Generator().manual_seed(40 + H)
+    C, N = 3, 16
+    conv = torch.randn(2, C, N, N, N, generator=g)
+    W1, b1 = torch.randn(H, C, generator=g) * 0.4, torch.randn(H, generator=g) * 0.1
+    W2, b2 = torch.randn(1, H, generator=g), torch.randn(1, generator=g)
+    V = filter_volumes([conv.to(dev)], W1, b1, W2, float(b2)).cpu()
+    want = orc.filter_mlp(conv.double().permute(0, 2, 3, 4, 1), W1.double(), b1.double(), W2.double(), b2.double())[..., 0]
+    assert V.shape == want.shape
+    assert (V.double() - want).abs().max() <= TOL * want.abs().max()
+
+
+@pytest.mark.parametrize("L,HP", [(32, 12), (48, 8)])
+def test_k3_refuses_a_width_or_box_outside_the_dispatch_table(dev, variants, L, HP):
+    """The raw call with valid pointers: a hidden width (12) or a box (48) that is not compiled is UNSUPPORTED, nothing runs."""
+    from deeplocalproteindocking_amd.engine import _ptr, _stream
+    N, C = 2 * L, 2
+    wsB = torch.zeros(1, C, L + 1, N, N, 2, device=dev)
+    V = torch.zeros(1, N, N, N, device=dev)
+    W1t, b1, W2 = torch.zeros(C, HP, device=dev), torch.zeros(HP, device=dev), torch.zeros(HP, device=dev)
+    with pytest.raises(RuntimeError, match="UNSUPPORTED"):
+        variants.call("dlpd_zifft_filter_form", _ptr(wsB), _ptr(V), 1, C, 0, L, _ptr(W1t), _ptr(b1), _ptr(W2), 0.0, HP, 0, 0.0,
+                      0.0, 0, 0, 0, 0, 0, 0, 0, 0, _stream(dev))
 
 
 def test_reference_class_default_hidden_width_48_is_fused(dev):

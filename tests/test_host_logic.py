@@ -52,7 +52,7 @@ def test_product_library_ships_one_formulation_per_box(built_lib):
     nm = subprocess.run(["nm", "-C", entry.LIB], capture_output=True, text=True).stdout
     assert "k_zifft_filter_rs<128" in nm and "k_zifft_filter_rs<160" in nm and "k_xy_corr_q4<160, true>" in nm and "k_xy_corr_s4<80, true>" in nm
     assert "k_zifft_filter<64," in nm and "k_zifft_filter<80," in nm                      # boxes 32 / 40: the one formulation there
-    for absent in ("k_rotate_zfft_cl_rs<", "k_xy_corr_quad<", "k_zifft_filter<128, 24, 1>", "k_zifft_filter_tiles<160", "k_zifft_filter<160, 24, 2>",
+    for absent in ("k_rotate_zfft_cl_rs<", "k_xy_corr_quad<", "k_zifft_filter<128, 24, 1>", "k_zifft_filter<160, 24, 1>", "k_zifft_filter<160, 24, 2>",
                    "k_zifft_filter<80, 24, 2>"):
         assert absent not in nm, absent
     assert built_lib.call("dlpd_orientation_supported", 64) == 1 and built_lib.call("dlpd_orientation_supported", 80) == 0
