@@ -132,7 +132,8 @@ class LocalDockingModel(nn.Module):
     requires a gradient (call it under ``torch.no_grad()``), rather than return a tensor that silently has no graph.
     ``differentiable=True`` (a public attribute; ``Training.LocalTrainer`` sets it on the model it is given) is the model that
     is trained: under autograd the correlation goes through the differentiable ``MultiplyVolumes`` (the adjoint kernel of
-    csrc/dlpd_local_grad.h), the representation runs as the plain torch modules it is made of, and the filter is CALLED -- the
+    csrc/dlpd_local_grad.h), the representation runs as the plain torch modules it is made of (with its ``hip_autograd`` set: its stride-1
+    convolutions on ``ops.conv3d_autograd``), and the filter is CALLED -- the
     fused filter kernel has no graph and serves ``torch.no_grad()`` only, as before.
     A filter that is not the reference's MLP (or is wider than the kernel's hidden widths) is called on the (B, sum C) features.
     ``forward_poses(receptor, ligand, R, T)`` scores P poses of ONE pair with one representation pass per protein (its docstring)."""

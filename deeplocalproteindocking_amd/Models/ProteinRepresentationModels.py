@@ -13,7 +13,10 @@ both plugins runs on the HIP kernels (``ops.conv3d`` -- f32 matrix cores, stride
 ``ops.maxpool3d_5s2``).  A layer shape those kernels do not cover is an error there, not a silent
 switch to torch/MIOpen: set ``DLPD_ALLOW_TORCH_CONV=1`` to allow it (a warning says which layer).
 On CPU tensors and under autograd the modules are plain torch (the reference implementation the
-tests compare against; training is outside this build).
+tests compare against) -- unless ``hip_autograd`` is set on the plugin (``LocalTrainer(hip_conv=True)``
+does): then, under autograd on a GPU, every stride-1 Conv3d(+ReLU) the kernels support runs forward AND
+backward on HIP (``ops.conv3d_autograd``: the forward kernel for the input gradient, csrc/dlpd_conv_grad.h
+for the weight gradient).  The max-pool and the SE3 plugin's one stride-2 layer stay on torch there.
 
 Loading reference checkpoints: ``E3MultiResRepr4x4`` loads ``*_repr_epochN.th`` of the reference
 as they are (identical module tree: ``conv1.{0,2,4,6,8}.weight``, ``conv2.{1,3,5,7}.weight``).
@@ -44,6 +47,12 @@ def _torch_conv_allowed(what):
 def _hip_inference(x, hip_lib):
     """The HIP kernels are the path: GPU tensors (or the emulated library of the test-suite), no autograd."""
     return (x.is_cuda or hip_lib is not None) and not torch.is_grad_enabled() and x.dtype == torch.float32
+
+
+def _hip_training(x, hip_lib):
+    """Where a plugin with ``hip_autograd`` set sends its stride-1 convolutions through ``ops.conv3d_autograd``: GPU
+    tensors (or the emulated library of the test-suite), float32, autograd on."""
+    return (x.is_cuda or hip_lib is not None) and torch.is_grad_enabled() and x.dtype == torch.float32
 
 
 class SyntheticRepr(Module):
@@ -101,6 +110,10 @@ class E3MultiResRepr4x4(Module):
     # lib: None -> the product library on a GPU; tests pass the emulated one
     hip_lib = None
     use_hip_conv = True
+    # Training on the HIP kernels (opt-in; LocalTrainer(hip_conv=True) sets it): under autograd every stride-1 Conv3d(+ReLU)
+    # the kernels support goes through ops.conv3d_autograd -- forward, input gradient and weight gradient
+    # (csrc/dlpd_conv_grad.h).  The max-pool stays on torch there.  False: under autograd the module is plain torch.
+    hip_autograd = False
     # skip the all-zero tiles of the bias-free convolutions (same bits; ops.conv3d); DLPD_TILE_OCCUPANCY=0: compute everywhere
     use_tile_occupancy = os.environ.get("DLPD_TILE_OCCUPANCY", "1") != "0"
     # Unwritten activations (round 6): inside ``with repr.outputs_with_maps():`` the tile-occupancy layers do not WRITE the
@@ -130,6 +143,7 @@ class E3MultiResRepr4x4(Module):
         from deeplocalproteindocking_amd import ops
         mods = list(seq)
         native = self.use_hip_conv and _hip_inference(x, self.hip_lib)
+        training = self.hip_autograd and self.use_hip_conv and _hip_training(x, self.hip_lib)
         # tile occupancy of x (ops.conv3d): the layers have no bias, so what lies outside the protein's neighbourhood stays
         # exactly zero from layer to layer and is not computed; one map is made of the input, every convolution writes its
         # output's and so does the pooling (None: unknown -- after a torch module -- and made again when a layer needs it);
@@ -153,6 +167,14 @@ class E3MultiResRepr4x4(Module):
                                             return_occupancy=True, unwritten=unwritten and m.stride[0] == 1)
                     else:
                         x = ops.conv3d(x, m.weight, relu=relu, lib=self.hip_lib, stride=m.stride[0])
+                    i += 2 if relu else 1
+                    continue
+            elif training and isinstance(m, nn.Conv3d):
+                if (m.bias is None and m.stride == (1, 1, 1) and m.dilation == (1, 1, 1) and m.groups == 1
+                        and m.padding == tuple(k // 2 for k in m.kernel_size) and cubic
+                        and ops.conv3d_supported(m.weight, x.shape[2], self.hip_lib)):
+                    relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                    x = ops.conv3d_autograd(x, m.weight, relu=relu, lib=self.hip_lib)
                     i += 2 if relu else 1
                     continue
             elif native and isinstance(m, nn.MaxPool3d):
@@ -252,6 +274,9 @@ class IsotropicConv3d(Module):
         return res
 
     hip_lib = None                     # tests: the emulated library
+    # under autograd: the stride-1 layer on ops.conv3d_autograd (E3MultiResRepr4x4.hip_autograd); the dense kernel's
+    # gradient flows on through the einsum of ``kernel()`` to the shell coefficients by torch
+    hip_autograd = False
 
     def load_radial_profile(self, dense_kernels):
         """For users who have se3cnn: its SE3Convolution([(cin, 0)], [(cout, 0)], size=5) of a reference checkpoint
@@ -275,6 +300,9 @@ class IsotropicConv3d(Module):
                   and x.shape[2] == x.shape[3] == x.shape[4] and ops.conv3d_supported(k, x.shape[2], self.hip_lib))
             if ok or not _torch_conv_allowed("IsotropicConv3d%s stride %d on %s" % (tuple(k.shape), self.stride, tuple(x.shape))):
                 return ops.conv3d(x, k, lib=self.hip_lib, stride=self.stride)      # f32 matrix cores
+        elif (self.hip_autograd and self.stride == 1 and _hip_training(x, self.hip_lib) and self.padding == k.shape[2] // 2
+              and x.dim() == 5 and x.shape[2] == x.shape[3] == x.shape[4] and ops.conv3d_supported(k, x.shape[2], self.hip_lib)):
+            return ops.conv3d_autograd(x, k, lib=self.hip_lib)
         return nn.functional.conv3d(x, k, padding=self.padding, stride=self.stride)
 
 
@@ -330,6 +358,12 @@ class SE3MultiResReprScalar(Module):
             res[name] = getattr(self, seq_name)[int(idx)].load_dense_kernel(kernels[name], exact=exact)
         return res
 
+    # opt-in, as E3MultiResRepr4x4.hip_autograd: handed to the layers at every call.  The stride-2 layer's backward stays on torch.
+    hip_autograd = False
+
     def forward(self, volume):
+        for m in self.modules():
+            if isinstance(m, IsotropicConv3d):
+                m.hip_autograd = self.hip_autograd
         vol1 = self.sequence_res0(volume)
         return [vol1, self.sequence_res1(vol1)]

@@ -5,7 +5,9 @@ lines.  ``data`` is the tuple ``(receptor_files, ligand_files, labels)`` a batch
 What differs is where the arithmetic runs: the atom front end is this build's ``Utils.FullAtom.CoordsBackend`` (in place of
 TorchProteinLibrary's PDB2CoordsUnordered / CoordsRotate / Coords2TypedCoords / getBBox / CoordsTranslate /
 TypedCoords2Volume), and the model's correlation and its backward are the HIP kernels of csrc/dlpd_local.h and
-csrc/dlpd_local_grad.h.  The representation's Conv3d layers train on torch's own kernels."""
+csrc/dlpd_local_grad.h.  The representation's Conv3d layers train on torch's own kernels by default; ``hip_conv=True``
+sends their stride-1 convolutions, forward and backward, through the HIP kernels as well (``ops.conv3d_autograd``,
+csrc/dlpd_conv_grad.h) -- the max-pool and a stride-2 layer stay on torch."""
 import atexit
 
 import torch
@@ -19,14 +21,21 @@ from deeplocalproteindocking_amd.Utils.FullAtom import CoordsBackend
 
 class LocalTrainer:
     def __init__(self, model, loss, lr=0.001, lr_decay=0.0001, box_size=120, resolution=1.0, add_neg=False, neg_weight=0.5,
-                 add_zero=False, zero_weight=1.0, randomize_rot=True, lib=None, conventions=None, rotation_seed=None):
+                 add_zero=False, zero_weight=1.0, randomize_rot=True, lib=None, conventions=None, rotation_seed=None,
+                 hip_conv=False):
         """lib: None -> the product library (GPU); the test-suite passes the emulated one (host tensors).  conventions: a
         ``Utils.Conventions.VolumeConventions`` (or the path of its JSON) for the projection's density shape and atom typing,
-        as ``Docker`` takes it.  rotation_seed: makes the random rotations reproducible (None: as ``Docker.random_rotation``)."""
+        as ``Docker`` takes it.  rotation_seed: makes the random rotations reproducible (None: as ``Docker.random_rotation``).
+        hip_conv: True sets ``hip_autograd`` on ``model.representation`` when it has that attribute (both plugins do): its
+        convolutions then train on the HIP kernels; False leaves the representation as it is."""
         self.lr = lr
         self.lr_decay = lr_decay
         self.model = model
         self.loss = loss
+        self.hip_conv = bool(hip_conv)
+        representation = getattr(self.model, "representation", None)
+        if self.hip_conv and hasattr(representation, "hip_autograd"):
+            representation.hip_autograd = True
         # the reference's driver builds LocalDockingModel(representation=, filter=) without a flag: the trainer is what makes
         # it the differentiable model
         if hasattr(self.model, "differentiable"):

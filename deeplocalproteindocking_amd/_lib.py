@@ -91,6 +91,8 @@ SIGNATURES = {
     "dlpd_conv3d_tile_occupancy_bytes": (_sz, [_i, _i]),
     "dlpd_conv3d_tile_occupancy": (_i, [_p, _p, _i, _i, _i, _p]),
     "dlpd_conv3d_split_sparse": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "dlpd_conv3d_wgrad_ws_floats": (_sz, [_i, _i, _i, _i]),
+    "dlpd_conv3d_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dlpd_topk_workspace_bytes": (_sz, [_i, _i]),
     "dlpd_topk_select": (_i, [_p, _i, _ll, _i, _p, _p, _p, _p]),
     "dlpd_topk_select_cand": (_i, [_p, _i, _ll, _i, _p, _p, _p, _p, _p, _i, _p]),

@@ -827,3 +827,5 @@ int dlpd_conv3d_strided(const float* x, const float* wp, float* y, int B, int ci
 }
 
 }  // extern "C"
+
+#include "dlpd_conv_grad.h"          // the weight gradient (dlpd_conv3d_wgrad): ConvCfg's staging, its own kernel family

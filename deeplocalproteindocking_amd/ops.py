@@ -9,6 +9,8 @@ TorchProteinLibrary's volume ops, backed by libdlpd.so.
     VolumeRotation also takes ONE (C,L,L,L) volume set for all B matrices, and is differentiable with respect to the
     volume (csrc/dlpd_rotate_grad.h), as the local correlations below are (local_correlate, local_correlate_rotated,
     MultiplyVolumes: csrc/dlpd_local_grad.h).  First order; R and T receive no gradient.
+    ``conv3d_autograd`` is the plugins' stride-1 convolution with both gradients on the HIP kernels
+    (``conv3d_input_grad``, ``conv3d_weight_grad``: csrc/dlpd_conv_grad.h); plain ``conv3d`` stays inference only.
 
 Everything else is inference only (the docking search runs under torch.no_grad(), local_test.py:67).
 Box sizes 32 / 40 / 64 / 80 run the compiled FFT pipeline, any other box (<= 128) a plan-free slow path.
@@ -293,6 +295,110 @@ def _packed_weights(weight, w, lib, device, split=False):
             _PACKED.clear()
         _PACKED[key] = wp
     return wp
+
+
+# Arithmetic of conv3d_autograd's forward and input gradient (None there = this).  Exact f32, not conv3d's split_bf16: the three
+# bf16 terms reproduce an f32 product to a few 1e-7, which inference does not see but a parameter gradient, held to twice
+# the error of a float32 evaluation, does (EXPERIMENTS.md, CONV-GRAD: 4.6-8.8 x that error at box 16 against 1.5-2.2 x).
+CONV_GRAD_PRECISION = "f32"
+CONV_WGRAD_PARTS = 256             # blocks the weight gradient's voxels are split over: a constant, so the bits are the machine's neighbour's too
+
+
+def _conv_volumes(t, name, lib):
+    t = _check(t, name, lib)
+    if t.dim() != 5 or not (t.shape[2] == t.shape[3] == t.shape[4]):
+        raise RuntimeError("dlpd: %s must be (B, C, D, D, D), got %s" % (name, tuple(t.shape)))
+    return t
+
+
+def conv3d_weight_grad(x, gy, ks, lib=None, nparts=None):
+    """gW (cout, cin, ks, ks, ks) of y = conv3d(x, w, padding=ks//2, stride=1, bias=None) for the upstream gradient gy:
+    gW[co, ci, d] = sum_b sum_v gy[b, co, v] x[b, ci, v + d - ks//2] (csrc/dlpd_conv_grad.h: exact f32 products on the matrix
+    cores, f32 accumulation).  x (B, cin, D, D, D), gy (B, cout, D, D, D) float32.  The sum runs over ``nparts`` fixed parts
+    of the voxels added in a fixed order (None: ``CONV_WGRAD_PARTS``): the same bits for the same nparts, on any device."""
+    lib_ = lib or get_lib()
+    x, gy = _conv_volumes(x, "x", lib), _conv_volumes(gy, "gy", lib)
+    B, cin, D, cout, ks = x.shape[0], x.shape[1], x.shape[2], gy.shape[1], int(ks)
+    if gy.shape[0] != B or gy.shape[2] != D or gy.device != x.device:
+        raise RuntimeError("dlpd: conv3d_weight_grad shape mismatch %s vs %s" % (tuple(x.shape), tuple(gy.shape)))
+    if not lib_.call("dlpd_conv3d_supported", cin, cout, ks, D):
+        raise RuntimeError("dlpd: conv3d_weight_grad has no HIP kernel for %d -> %d channels, kernel %d, box %d (supported: "
+                           "kernel 3 or 5, output channels a multiple of 16, box <= 80)" % (cin, cout, ks, D))
+    nparts = int(CONV_WGRAD_PARTS if nparts is None else nparts)
+    ws = torch.empty(lib_.call("dlpd_conv3d_wgrad_ws_floats", cin, cout, ks, nparts), dtype=torch.float32, device=x.device)
+    gw = torch.empty(cout, cin, ks, ks, ks, dtype=torch.float32, device=x.device)
+    lib_.call("dlpd_conv3d_wgrad", _ptr(x), _ptr(gy), _ptr(gw), _ptr(ws), B, cin, cout, D, ks, nparts, _stream(x.device))
+    return gw
+
+
+CONV_GX_GROUP = 8                  # output channels of the layer summed by one call of the forward kernel in conv3d_input_grad
+
+
+def conv3d_input_grad(gy, weight, lib=None, precision=None):
+    """gX (B, cin, D, D, D) of the same stride-1 layer: the FORWARD kernel applied to gy with the taps flipped and the channel
+    axes exchanged (any ``precision`` of ``conv3d``; the weights are packed per call).  The forward kernel adds all its
+    cout * k^3 terms in one running sum; here the layer's output channels go through it in groups of ``CONV_GX_GROUP`` whose
+    results are added in ascending order -- a sum of sums, which is what holds a plugin's parameter gradients to the error
+    of a float32 evaluation (EXPERIMENTS.md, CONV-GRAD).  It needs the layer's cin to be a multiple of 16 -- every layer of
+    both plugins but the first, whose input needs no gradient.  Where it cannot run it is an error, unless
+    DLPD_ALLOW_TORCH_CONV=1: then ``torch.nn.grad.conv3d_input`` does it, with a warning."""
+    gy = _conv_volumes(gy, "gy", lib)
+    w = weight.detach().to(device=gy.device, dtype=torch.float32)
+    if w.dim() != 5 or w.shape[0] != gy.shape[1]:
+        raise RuntimeError("dlpd: conv3d_input_grad channel mismatch %s vs %s" % (tuple(w.shape), tuple(gy.shape)))
+    wt = w.flip(2, 3, 4).transpose(0, 1).contiguous()               # (cin, cout, k, k, k): a layer from cout to cin channels
+    if not conv3d_supported(wt, gy.shape[2], lib):
+        from .Models.ProteinRepresentationModels import _torch_conv_allowed
+        _torch_conv_allowed("the input gradient of Conv3d%s on %s" % (tuple(w.shape), tuple(gy.shape)))      # (raises unless allowed)
+        size = (gy.shape[0], w.shape[1]) + tuple(gy.shape[2:])
+        return torch.nn.grad.conv3d_input(size, w, gy, padding=w.shape[2] // 2)
+    gx = None
+    for beg in range(0, w.shape[0], CONV_GX_GROUP):
+        part = conv3d(gy[:, beg:beg + CONV_GX_GROUP].contiguous(), wt[:, beg:beg + CONV_GX_GROUP].contiguous(), lib=lib, precision=precision)
+        gx = part if gx is None else gx.add_(part)
+    return gx
+
+
+class _Conv3d(torch.autograd.Function):
+    """conv3d_autograd: the forward is the plain call; the backward masks the upstream gradient by the ReLU and runs
+    conv3d_input_grad / conv3d_weight_grad for the inputs that need a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, relu, lib, precision):
+        # (weight.detach(): not the nn.Parameter, so packed per call -- conv3d's cache of packed parameters, which synchronises
+        #  the stream when it publishes an entry, would be refilled after every optimizer step)
+        y = conv3d(x.detach(), weight.detach(), relu=relu, lib=lib, precision=precision)
+        ctx.save_for_backward(x, weight, y if relu else None)
+        ctx.args = (relu, lib, precision)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, weight, y = ctx.saved_tensors
+        relu, lib, precision = ctx.args
+        gy = _check(gy, "the gradient", lib)
+        if relu:
+            gy = gy * (y > 0).to(gy.dtype)
+        gx = conv3d_input_grad(gy, weight, lib=lib, precision=precision) if ctx.needs_input_grad[0] else None
+        gw = None
+        if ctx.needs_input_grad[1]:
+            gw = conv3d_weight_grad(x.detach(), gy, weight.shape[2], lib=lib).to(device=weight.device, dtype=weight.dtype)
+        return gx, gw, None, None, None
+
+
+def conv3d_autograd(x, weight, relu=False, lib=None, precision=None):
+    """``conv3d(x, weight, relu=relu)`` (stride 1) that autograd can differentiate: first order, with respect to ``x`` and
+    ``weight``, both on the HIP kernels (the forward kernel for gX, csrc/dlpd_conv_grad.h for gW).  Plain ``conv3d`` stays
+    inference only; this is the call the plugins make with ``hip_autograd`` set.  precision: of the forward and of gX, None =
+    ``CONV_GRAD_PRECISION`` (gW is always exact f32).  Without autograd it is ``conv3d`` at that precision."""
+    precision = precision or CONV_GRAD_PRECISION
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
+        x = _conv_volumes(x, "x", lib)
+        if weight.dim() != 5 or not conv3d_supported(weight, x.shape[2], lib):
+            raise RuntimeError("dlpd: conv3d_autograd has no HIP kernel for weights %s on %s" % (tuple(weight.shape), tuple(x.shape)))
+        return _Conv3d.apply(x, weight, bool(relu), lib, precision)
+    return conv3d(x, weight, relu=relu, lib=lib, precision=precision)
 
 
 def maxpool3d_5s2(x, lib=None, occupancy=None, return_occupancy=False, unwritten=False):

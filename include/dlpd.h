@@ -393,6 +393,19 @@ int dlpd_conv3d_tile_occupancy(const float* x, unsigned char* occ, int B, int ci
 int dlpd_conv3d_split_sparse(const float* x, const void* wp, float* y, const unsigned char* occ_in, unsigned char* occ_out,
                              int B, int cin, int cout, int D, int ks, int relu, int stride, int unwritten, void* stream);
 
+/* The convolution's gradient with respect to its weights -- what L.backward() in the reference's trainer
+ * (src/Training/LocalTrainer.py, optimize) asks of every Conv3d of the representation plugins:
+ *   gw (cout, cin, ks^3) = sum over b and voxels v of gy (B, cout, D^3)[b, co, v] * x (B, cin, D^3)[b, ci, v + tap - ks/2]
+ * for the stride-1 layer y = conv3d(x, w, padding ks/2), zeros outside the box; exact f32 products on the matrix cores, f32
+ * accumulation.  Shapes: those of dlpd_conv3d_supported, any B; stride 2 is not supported.  The voxels are split over
+ * `nparts` blocks in a fixed order (block p takes the patches p, p + nparts, ...), each writes its partial gw to ws
+ * (dlpd_conv3d_wgrad_ws_floats() floats) and the partials are added in ascending p: no float atomics, the same bits for the
+ * same nparts on every run and device.  (The gradient with respect to x is dlpd_conv3d / dlpd_conv3d_split on gy with the
+ * flipped, transposed weights.) */
+size_t dlpd_conv3d_wgrad_ws_floats(int cin, int cout, int ks, int nparts);
+int dlpd_conv3d_wgrad(const float* x, const float* gy, float* gw, float* ws, int B, int cin, int cout, int D, int ks,
+                      int nparts, void* stream);
+
 /* MaxPool3d(kernel 5, stride 2, padding 2) of the E3 plugin (ProteinRepresentationModels.py:101):
  * x (nvol, D^3) -> y (nvol, Do^3), Do = (D - 1) / 2 + 1. */
 int dlpd_maxpool3d_5s2(const float* x, float* y, int nvol, int D, void* stream);
