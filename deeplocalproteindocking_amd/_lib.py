@@ -60,6 +60,10 @@ SIGNATURES = {
     "dlpd_rotated_occupancy": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
     "dlpd_zfft_channels_last_occ": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
     "dlpd_pencil_map_supported": (_i, [_i]),
+    "dlpd_channel_chunks_floats": (ctypes.c_size_t, [_i, _i]),
+    "dlpd_channel_chunks_default": (_i, [_i]),
+    "dlpd_make_channel_chunks": (_i, [_p, _p, _i, _i, _p]),
+    "dlpd_zfft_channel_chunks": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
     "dlpd_pencil_bits": (_i, [_p, _p, _i, _i, _p]),
     "dlpd_xy_correlate_packed_occ": (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _p]),
     "dlpd_xy_correlate_oriented": (_i, [_p, _p, _p, _i, _i, _i, _ll, _i, _p]),
@@ -132,7 +136,7 @@ class DlpdLib:
     def call(self, name, *args):
         rc = getattr(self, "_" + name)(*args)
         if SIGNATURES[name][0] is _i and name not in ("dlpd_version", "dlpd_grid_supported", "dlpd_conv3d_supported", "dlpd_orientation_supported",
-                                                      "dlpd_hidden_pad", "dlpd_fused_hidden_pad", "dlpd_generic_box_supported", "dlpd_debug_poison_selfcheck", "dlpd_k1_form_supported", "dlpd_pencil_map_supported", "dlpd_local_max_poses") and rc != 0:
+                                                      "dlpd_hidden_pad", "dlpd_fused_hidden_pad", "dlpd_generic_box_supported", "dlpd_debug_poison_selfcheck", "dlpd_k1_form_supported", "dlpd_pencil_map_supported", "dlpd_channel_chunks_default", "dlpd_local_max_poses") and rc != 0:
             raise RuntimeError("dlpd: %s failed: %s" % (name, ERRORS.get(rc, rc)))
         return rc
 

@@ -270,6 +270,11 @@ k_rotate_zfft(const float* __restrict__ vol, const float* __restrict__ R, cplx* 
 //   one L2.  LDS: 64 pencils x (N + 13) complex; the pencils of channel quad q start SKEW q elements into their
 //   rows, which puts the 8-byte stores of a voxel's lanes (channel quads 4 YG/2 pencils apart: same bank otherwise)
 //   on disjoint banks.
+// The source is addressed as cl[chunk * cstride + voxel * vstride + q] (float4 units; q = the lane's channel quad inside
+// the block's CC channels), which covers both copies: channels-last cl[x][y][z][Cp] (vstride = Cp / 4, cstride = CC / 4)
+// and CHUNK-MAJOR [chunk][x][y][z][CC] (vstride = CC / 4, cstride = L^3 CC / 4; dlpd_make_channel_chunks), where a
+// block's CC channels of neighbouring z fill whole 128-byte lines instead of a CC-channel slice of each voxel's record.
+// Only addresses differ: same samples, same spectra.
 // ------------------------------------------------------------------------------------------
 // OCC (round 6, its own instantiation: the dense callers run the code they always ran): `occ` (nb, ceil(L/4)^3) bytes,
 // [x cell][y cell][z cell] per rotation, 0 = every sample of that 4 x 4 x 4 cell of the ROTATED volume is zero
@@ -279,8 +284,8 @@ k_rotate_zfft(const float* __restrict__ vol, const float* __restrict__ R, cplx* 
 // and writes its zeros.  Exact; same spectra as without the map.
 template <int N, bool OCC> __global__ void __launch_bounds__(K1ClCfg<N>::NP * FftPlan<N>::T)
 k_rotate_zfft_cl(const float4* __restrict__ cl, const float* __restrict__ R, cplx* __restrict__ A,
-                 int C, int Cq, int nb, float c0, int CT_out, int c_base, int ext, const unsigned char* __restrict__ occ,
-                 int skip_empty) {
+                 int C, int nchunk, int vstride, int cstride, int nb, float c0, int CT_out, int c_base, int ext,
+                 const unsigned char* __restrict__ occ, int skip_empty) {
   constexpr int L = N / 2, NZ = N / 2 + 1, NP = K1ClCfg<N>::NP, CC = K1ClCfg<N>::CC, YG = K1ClCfg<N>::YG, NPR = YG / 2;
   constexpr int LPV = CC / 4, SKEW = 16 / LPV;         // lanes per voxel; bank skew (complex) between channel quads
   static_assert(CC * NPR == NP && L % YG == 0 && (NP * FftPlan<N>::T) % 64 == 0, "whole waves of pencils per block");
@@ -290,12 +295,16 @@ k_rotate_zfft_cl(const float4* __restrict__ cl, const float* __restrict__ R, cpl
   DLPD_DYN_SHARED(cplx, S);
   cplx* tw = S + NP * RS;
   const int tid = threadIdx.x;
-  const int nchunk = Cq / (CC / 4), per = (L / YG) * nchunk;
+  const int per = (L / YG) * nchunk;
   const int groups = nb * L, gper = (groups + 7) / 8;
   const int bid = blockIdx.x, seq = bid >> 3;
   const int g = (bid & 7) * gper + seq / per;
   if (seq / per >= gper || g >= groups) return;
+#ifdef DLPD_K1_CHUNK_OUTER                                      // (A/B builds: the row groups of one chunk are neighbours)
+  const int inner = seq % per, chunk = inner / (L / YG), yg = inner % (L / YG);
+#else
   const int inner = seq % per, yg = inner / nchunk, chunk = inner % nchunk;
+#endif
   const int b = g / L, x = g % L;
   constexpr int NC = (L + 3) / 4, YC = YG / 4;                 // cells per axis; y cells of a block's rows
   static_assert(YG % 4 == 0, "a block's rows are whole cells");
@@ -328,12 +337,12 @@ k_rotate_zfft_cl(const float4* __restrict__ cl, const float* __restrict__ R, cpl
     const K1ClRot rot = k1cl_load_rotation(R + (size_t)b * 9);
     for (int task = tid; task < NPR * L * LPV; task += NT) {
       const int q = task % LPV, z = (task / LPV) % L, m = (task / LPV) / L;
-      const float4* src = cl + chunk * (CC / 4) + q;
+      const float4* src = cl + (size_t)chunk * cstride + q;
       float4 acc[2];
       if (OCC && !occ_s[((2 * m) >> 2) * NC + (z >> 2)])       // rows 2m, 2m + 1 lie in one cell
         acc[0] = acc[1] = make_float4(0.f, 0.f, 0.f, 0.f);
       else
-        k1cl_sample_rows(src, Cq, L, ext, c0, rot, x, yg * YG + 2 * m, z, acc);
+        k1cl_sample_rows(src, vstride, L, ext, c0, rot, x, yg * YG + 2 * m, z, acc);
       // rows 2m (real part) and 2m+1 (imaginary part) of the four channels' pencils
       cplx* P = S + ((4 * q) * NPR + m) * RS + SKEW * q + z;
       P[0] = c_make(acc[0].x, acc[1].x);
@@ -391,23 +400,44 @@ __global__ void __launch_bounds__(256) k_make_channels_last(const float* __restr
   }
 }
 
+// (C, L, L, L) -> chunk-major (nchunk, L, L, L, 4 CCq): chunk k holds channels [4 CCq k, 4 CCq (k + 1)), zero padded
+__global__ void __launch_bounds__(256) k_make_channel_chunks(const float* __restrict__ v, float4* __restrict__ out, int C, int CCq,
+                                                             int nchunk, int L) {
+  const size_t L3 = (size_t)L * L * L, total = L3 * CCq * nchunk;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int q = (int)(i % CCq);
+    const size_t vox = (i / CCq) % L3;
+    const int c0 = 4 * ((int)(i / (CCq * L3)) * CCq + q);
+    float e[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) e[j] = (c0 + j < C) ? v[(size_t)(c0 + j) * L3 + vox] : 0.f;
+    out[i] = make_float4(e[0], e[1], e[2], e[3]);
+  }
+}
+
+// chunk_major: `cl` is the copy of dlpd_make_channel_chunks (chunks of K1ClCfg<N>::CC channels), else dlpd_make_channels_last's
 template <int N> static int launch_k1_cl(const float4* cl, const float* R, cplx* A, int C, int nb, float c0, hipStream_t st,
-                                         int CT_out, int c_base, int ext = 0, const unsigned char* occ = nullptr, int skip_empty = 0) {
-  constexpr int L = N / 2, RS = N + DLPD_K1CL_PAD;
+                                         int CT_out, int c_base, int ext = 0, const unsigned char* occ = nullptr, int skip_empty = 0,
+                                         bool chunk_major = false) {
+  constexpr int L = N / 2, RS = N + DLPD_K1CL_PAD, CCq = K1ClCfg<N>::CC / 4;
   const int Cq = ((C + DLPD_K1CL_CC - 1) / DLPD_K1CL_CC) * (DLPD_K1CL_CC / 4);
+  const int nchunk = chunk_major ? (C + 4 * CCq - 1) / (4 * CCq) : Cq / CCq;
+  const int vstride = chunk_major ? CCq : Cq, cstride = chunk_major ? L * L * L * CCq : CCq;
   const size_t shmem = (size_t)(K1ClCfg<N>::NP * RS + N) * sizeof(cplx);
-  const int per = (L / K1ClCfg<N>::YG) * (Cq / (K1ClCfg<N>::CC / 4));
+  const int per = (L / K1ClCfg<N>::YG) * nchunk;
   const int gper = (nb * L + 7) / 8;
   dim3 grid((unsigned)(8 * gper * per)), block(K1ClCfg<N>::NP * FftPlan<N>::T);
   const int e = (ext > 0 && ext < L) ? ext : L;
   if (occ) {
     int rc = dlpd_set_max_dyn_shared((const void*)k_rotate_zfft_cl<N, true>, shmem);
     if (rc) return rc;
-    DLPD_LAUNCH((k_rotate_zfft_cl<N, true>), grid, block, shmem, st, cl, R, A, C, Cq, nb, c0, CT_out, c_base, e, occ, skip_empty);
+    DLPD_LAUNCH((k_rotate_zfft_cl<N, true>), grid, block, shmem, st, cl, R, A, C, nchunk, vstride, cstride, nb, c0, CT_out,
+                c_base, e, occ, skip_empty);
   } else {
     int rc = dlpd_set_max_dyn_shared((const void*)k_rotate_zfft_cl<N, false>, shmem);
     if (rc) return rc;
-    DLPD_LAUNCH((k_rotate_zfft_cl<N, false>), grid, block, shmem, st, cl, R, A, C, Cq, nb, c0, CT_out, c_base, e, occ, 0);
+    DLPD_LAUNCH((k_rotate_zfft_cl<N, false>), grid, block, shmem, st, cl, R, A, C, nchunk, vstride, cstride, nb, c0, CT_out,
+                c_base, e, occ, 0);
   }
   return dlpd_check_launch();
 }
@@ -1207,6 +1237,44 @@ int dlpd_zfft_channels_last_occ(const float* cl, const float* R, const unsigned 
   const float4* c4 = (const float4*)cl;
   return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
     return launch_k1_cl<2 * l()>(c4, R, A, C, nb, center, st, CT_out, c_base, extent, occ, skip_empty);
+  });
+}
+
+// The chunk-major copy (include/dlpd.h): chunks of K1ClCfg<2L>::CC channels, the block width of k_rotate_zfft_cl at that box
+#ifndef DLPD_K1_CHUNK_MAJOR_BOXES
+#define DLPD_K1_CHUNK_MAJOR_BOXES 64        // boxes whose engine gathers from it by default (EXPERIMENTS.md)
+#endif
+static int k1_chunk_channels(int L) {
+  int cc = 0;
+  dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) { cc = K1ClCfg<2 * l()>::CC; return DLPD_OK; });
+  return cc;
+}
+int dlpd_channel_chunks_default(int L) { return dlpd_listed<DLPD_K1_CHUNK_MAJOR_BOXES>(L) ? 1 : 0; }
+
+size_t dlpd_channel_chunks_floats(int C, int L) {
+  const int cc = k1_chunk_channels(L);
+  return (cc && C > 0) ? (size_t)L * L * L * (size_t)(((C + cc - 1) / cc) * cc) : 0;
+}
+
+int dlpd_make_channel_chunks(const float* vol, float* buf, int C, int L, void* stream) {
+  if (!vol || !buf || C <= 0 || L <= 0) return DLPD_ERR_ARG;
+  const int cc = k1_chunk_channels(L);
+  if (!cc) return DLPD_ERR_UNSUPPORTED;
+  const int nchunk = (C + cc - 1) / cc;
+  const size_t total = (size_t)L * L * L * (cc / 4) * nchunk;
+  size_t nblk = (total + 255) / 256;
+  if (nblk > 65536) nblk = 65536;
+  DLPD_LAUNCH(k_make_channel_chunks, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, vol, (float4*)buf, C, cc / 4, nchunk, L);
+  return dlpd_check_launch();
+}
+
+// K1 from the chunk-major copy: dense (occ null), embedded extent, or by occupancy maps -- one entry
+int dlpd_zfft_channel_chunks(const float* buf, const float* R, const unsigned char* occ, void* wsA, int nb, int C, int CT_out,
+                             int c_base, int L, float center, int extent, int skip_empty, void* stream) {
+  if (!buf || !R || !wsA || nb <= 0 || C <= 0 || c_base < 0 || c_base + C > CT_out || extent < 0 || extent > L) return DLPD_ERR_ARG;
+  return dlpd_dispatch<DLPD_BOXES>(L, [&](auto l) {
+    return launch_k1_cl<2 * l()>((const float4*)buf, R, (cplx*)wsA, C, nb, center, (hipStream_t)stream, CT_out, c_base, extent, occ,
+                                 occ ? skip_empty : 0, true);
   });
 }
 

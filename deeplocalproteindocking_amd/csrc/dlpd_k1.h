@@ -24,14 +24,26 @@
 //    0.686 ms (32-byte gathers), as 4 rows x 16 channels 1.67 ms (32-byte OUTPUT runs: 2.7 x), 16 rows x 8 channels
 //    re-measured 0.675, against 0.61 for 8 x 16; 48 ch x 80^3: 1.93 / 3.65 / 2.12 against 1.71.  Occupancy is not what this
 //    kernel lacks; the run lengths of its gathers and stores are what it pays for.
+// The SOURCE layout (EXPERIMENTS.md, K1 chunk-major): k_rotate_zfft_cl addresses the copy as chunk * cstride + voxel * vstride + q,
+// so the same kernel reads cl[x][y][z][Cp] and the chunk-major [chunk][x][y][z][CC] (dlpd_make_channel_chunks; CC = this
+// struct's CC, so the copy follows the block shape).  At N = 128 (48 channels, launches of 32 rotations) a 16 x 8 block used 32
+// bytes of every 128-byte line of the channels-last records; chunk-major, TCP -> TCC read requests per launch fall 2.35e8 ->
+// 0.92e8 (2.55 x), tag accesses 4.37e8 -> 3.98e8, and the launch 1.60 -> 1.37 ms: line fills were about a seventh of the
+// kernel, the rest is its (lane, instruction) request count, which the layout does not change.  Re-measured under the new
+// layout (ms per launch / per step of 32 rotations, same session): 16 x 8 1.35 / 9.57, 8 x 16 1.40 / 9.63, 32 x 4 (4-channel
+// chunks, eight z-neighbours per line) 2.23 / 10.59; blocks of one chunk adjacent (row group inside chunk, -DDLPD_K1_CHUNK_OUTER)
+// 1.40 / 9.63 against chunk inside row group 1.35 / 9.57.  Shape and order stay as they were.
 #ifndef DLPD_K1_YG160
 #define DLPD_K1_YG160 8
 #endif
 #ifndef DLPD_K1_CC160
 #define DLPD_K1_CC160 16
 #endif
+#ifndef DLPD_K1_YG128
+#define DLPD_K1_YG128 16
+#endif
 template <int N> struct K1ClCfg {
-  static constexpr int YG = (N == 128) ? 16 : (N == 160 ? DLPD_K1_YG160 : 8), CC = (N == 160) ? DLPD_K1_CC160 : 128 / YG;
+  static constexpr int YG = (N == 128) ? DLPD_K1_YG128 : (N == 160 ? DLPD_K1_YG160 : 8), CC = (N == 160) ? DLPD_K1_CC160 : 128 / YG;
   static constexpr int NP = CC * (YG / 2);             // two-row pencils per block
 };
 struct K1ClRot { float r0, r1, r2, r3, r4, r5, r6, r7, r8; };

@@ -126,7 +126,12 @@ class _Grid:
         self.extent, self.rot_scale = extent, float(rot_scale)
         N, NZ = self.N, self.NZ
         self.lig = torch.zeros(CT, L, L, L, dtype=f32, device=dev)
-        self.ligcl = torch.empty(lib.call("dlpd_channels_last_floats", C, L), dtype=f32, device=dev) if eng.use_cl else None
+        # ... in chunk-major order where the engine asks for it or the library prefers it at this box (include/dlpd.h,
+        # dlpd_make_channel_chunks); the role-split K1 formulation reads the channels-last order only
+        want = eng.k1_chunk_major if eng.k1_chunk_major is not None else bool(lib.call("dlpd_channel_chunks_default", L))
+        self.chunk_major = bool(eng.use_cl and want and eng._k1_form_at(L) in (0, 1))
+        self.ligcl = torch.empty(lib.call("dlpd_channel_chunks_floats" if self.chunk_major else "dlpd_channels_last_floats", C, L),
+                                 dtype=f32, device=dev) if eng.use_cl else None
         self.ligq = torch.empty(lib.call("dlpd_quads_floats", CT, L), dtype=f32, device=dev) if eng.use_quads else None
         # boxes whose K2 re-reads the receptor spectrum for every rotation (80, 40) take a copy in the order its column
         # phase consumes it (include/dlpd.h: dlpd_receptor_pack); written by set_receptor, read by untransposed launches
@@ -156,7 +161,8 @@ class DockingEngine:
                  fine_unfused=None, channels_last=None, k3_form=0, coarse_center=None, extent=None,
                  orient=True, quads=True, prefilter=True, packed_receptor=True,
                  rotation_scale=1.0, coarse_rotation_scale=None, rotation_axis_order="xyz", clip_mode="output",
-                 rotation_transpose=False, keep_receptor_spectrum=False, k1_form=0, sparse_k1=None):
+                 rotation_transpose=False, keep_receptor_spectrum=False, k1_form=0, sparse_k1=None,
+                 k1_chunk_major=None):
         """coarse_channels > 0: the reference's two-resolution layout -- C channels at L^3 plus
         ``coarse_channels`` at (L/2)^3 (ProteinRepresentationModels.py:72-76); W1 is (H, C+coarse).
         extent < L: the volumes are extent^3 boxes in the corner of the L^3 ones (a box size without a compiled plan
@@ -222,6 +228,9 @@ class DockingEngine:
         if channels_last is None:
             channels_last = self.C >= 8
         self.use_cl = bool(channels_last)
+        # source layout of the channels-last K1: None = the library's choice per box, True / False = the chunk-major copy
+        # ([chunk][x][y][z][CC]) or the channels-last one ([x][y][z][Cp]) on every grid; same spectra either way
+        self.k1_chunk_major = None if k1_chunk_major is None else bool(k1_chunk_major)
         self.extent = int(extent) if extent and int(extent) < int(L) else 0
         if self.extent and self.clip_mode == "input":
             raise RuntimeError("dlpd: clip_mode 'input' is not combined with embedded boxes (use a compiled box size)")
@@ -293,7 +302,9 @@ class DockingEngine:
     def switches(self):
         """Which of the equivalent kernel formulations and which conventions this engine launches with (bench.py records it)."""
         fine, c = self.fine, self.coarse
+        layout = lambda g: None if not (g and self.use_cl) else ("chunk_major" if g.chunk_major else "channels_last")
         return {"k1": "channels_last" if self.use_cl else "per_channel",
+                "k1_source_layout": {"fine": layout(fine), "coarse": layout(c)},
                 "k1_slab_orientation": bool(self.orient), "k1_quad_layout": bool(self.use_quads),
                 "k1_form": {0: "library default", 1: "phased", 2: "role-split"}[self.k1_form],
                 "k3_form": {0: "library default (role-split where compiled)", 1: "channel-owning", 2: "role-split"}[self.k3_form],
@@ -392,7 +403,8 @@ class DockingEngine:
         st = _stream(self.device)
         for g in self.grids:
             if self.use_cl:
-                self.lib.call("dlpd_make_channels_last", _ptr(g.lig), _ptr(g.ligcl), g.C, g.L, st)
+                self.lib.call("dlpd_make_channel_chunks" if g.chunk_major else "dlpd_make_channels_last", _ptr(g.lig), _ptr(g.ligcl),
+                              g.C, g.L, st)
             elif self.use_quads:
                 self.lib.call("dlpd_make_quads", _ptr(g.lig), _ptr(g.ligq), g.CT, g.L, st)
         self._ligand_occupancy()
@@ -424,9 +436,12 @@ class DockingEngine:
             if g.sparse and self._k1_form_at(L) in (0, 1):
                 pen = g.pen if g.pencil_map else None
                 call("dlpd_rotated_occupancy", _ptr(g.occ_src), _ptr(R), _ptr(g.occ_rot), _ptr(pen), nb, L, c0, st)
-                call("dlpd_zfft_channels_last_occ", _ptr(g.ligcl), _ptr(R), _ptr(g.occ_rot), _ptr(g.wsA), nb, g.C, g.CT, 0, L,
-                     c0, g.extent, int(g.pencil_map), st)
+                call("dlpd_zfft_channel_chunks" if g.chunk_major else "dlpd_zfft_channels_last_occ", _ptr(g.ligcl), _ptr(R),
+                     _ptr(g.occ_rot), _ptr(g.wsA), nb, g.C, g.CT, 0, L, c0, g.extent, int(g.pencil_map), st)
                 return pen
+            if g.chunk_major:
+                call("dlpd_zfft_channel_chunks", _ptr(g.ligcl), _ptr(R), 0, _ptr(g.wsA), nb, g.C, g.CT, 0, L, c0, g.extent, 0, st)
+                return None
             call("dlpd_zfft_channels_last_form", _ptr(g.ligcl), _ptr(R), _ptr(g.wsA), nb, g.C, g.CT, 0, L, c0, g.extent,
                  self._k1_form_at(L), st)
         elif quads:

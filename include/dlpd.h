@@ -164,6 +164,18 @@ int dlpd_zfft_channels_last_occ(const float* cl, const float* R, const unsigned 
 int dlpd_pencil_map_supported(int L);
 int dlpd_xy_correlate_packed_occ(const void* wsA, const void* rec_packed, void* wsB, int nb, int CT, int L,
                                  const unsigned* pencil_map, int nmasked, void* stream);
+/* CHUNK-MAJOR copy of the same C score volumes: buf[chunk][x][y][z][CC], CC = the channels one K1 block transforms at that
+ * box (8 at box 64, 16 at the others), channels zero padded to whole chunks -- never larger than the channels-last copy.
+ * A K1 block gathers CC channels of each corner; in cl[x][y][z][Cp] those are a CC-channel slice of every voxel's record (at
+ * 48 channels and box 64: 32 of every 128-byte line it pulls into its L1), here the CC channels of neighbouring z are
+ * adjacent and the block uses every line it fetches whole.  dlpd_zfft_channel_chunks is dlpd_zfft_channels_last_ext (occ
+ * null) / dlpd_zfft_channels_last_occ (occ given; skip_empty as there) reading this copy: only addresses differ, the spectra
+ * are bit-identical.  dlpd_channel_chunks_default(L): 1 where the engine gathers from this copy unless told otherwise. */
+size_t dlpd_channel_chunks_floats(int C, int L);
+int dlpd_channel_chunks_default(int L);
+int dlpd_make_channel_chunks(const float* vol, float* buf, int C, int L, void* stream);
+int dlpd_zfft_channel_chunks(const float* buf, const float* R, const unsigned char* occ, void* wsA, int nb, int C, int CT_out,
+                             int c_base, int L, float center, int extent, int skip_empty, void* stream);
 
 /* CoordsRotate + CoordsTranslate + TypedCoords2Volume (+ channel sum) of src/Docker/Docker.py:204,
  * 208,221-224 in one kernel: p' = R_b p + shift, density exp(-|r - p'|^2 / 2) on the 5^3 voxels
