@@ -381,10 +381,11 @@ class Docker:
             if was_training:
                 model.train()
 
-    def _score_poses(self, receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius):
-        from deeplocalproteindocking_amd import ops
+    def _pose_inputs(self, receptor_volumes, ligand_volumes, receptor_forbidden, ligand_forbidden, clash_provider):
+        """What scoring given poses needs on the device, by the search's conventions: the volumes per resolution, fine / coarse
+        edge, the clip the features take, the forbidden volumes (rf; lf None with a provider)."""
         model = self.docking_model
-        dev, lib = self.device, self._lib
+        dev = self.device
         rec = [torch.as_tensor(v, dtype=torch.float32) for v in receptor_volumes]
         lig = [torch.as_tensor(v, dtype=torch.float32) for v in ligand_volumes]
         rec = [v.reshape((-1,) + tuple(v.shape[-3:])).to(dev).contiguous() for v in rec]
@@ -402,6 +403,21 @@ class Docker:
         if clip is not None and cv.clip_mode == "input":
             rec, lig = [v.clamp(-float(clip), float(clip)) for v in rec], [v.clamp(-float(clip), float(clip)) for v in lig]
             clip = None
+        rf = lf = None
+        if receptor_forbidden is not None:
+            rf = torch.as_tensor(receptor_forbidden, dtype=torch.float32).reshape(1, L, L, L).to(dev).contiguous()
+            if clash_provider is None:
+                lf = torch.as_tensor(ligand_forbidden, dtype=torch.float32).reshape(1, L, L, L).to(dev).contiguous()
+        return rec, lig, scale, clip, rf, lf
+
+    def _score_poses(self, receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius):
+        from deeplocalproteindocking_amd import ops
+        model = self.docking_model
+        dev, lib = self.device, self._lib
+        cv = self.conventions
+        rec, lig, scale, clip, rf, lf = self._pose_inputs(receptor_volumes, ligand_volumes, receptor_forbidden, ligand_forbidden,
+                                                          clash_provider)
+        L = rec[0].shape[-1]
         R = torch.as_tensor(np.asarray(R, dtype=np.float64) if not torch.is_tensor(R) else R).reshape(-1, 3, 3)
         T = torch.as_tensor(np.asarray(T) if not torch.is_tensor(T) else T).reshape(-1, 3)
         P, r = R.shape[0], int(radius)
@@ -409,12 +425,7 @@ class Docker:
             raise Exception("score_poses: one translation per rotation", T.shape[0], P)
         Td = T.to(torch.int32).to(dev).contiguous()
         Rf = R.to(device=dev, dtype=torch.float32).contiguous()
-        has_clash = receptor_forbidden is not None
-        if has_clash:
-            rf = torch.as_tensor(receptor_forbidden, dtype=torch.float32).reshape(1, L, L, L).to(dev).contiguous()
-            lf = None
-            if clash_provider is None:
-                lf = torch.as_tensor(ligand_forbidden, dtype=torch.float32).reshape(1, L, L, L).to(dev).contiguous()
+        has_clash = rf is not None
         params = fused_filter_parameters(model)
         W = 2 * r + 1
         out = torch.empty(P, W, W, W, dtype=torch.float32, device=dev)
@@ -524,6 +535,150 @@ class Docker:
                 return be.project(lc, ln, lo, L, res, dev, R=Rb, shift=self.box_center, sum_types=True)
             return self.refine(prepared.receptor_volumes, prepared.ligand_volumes, prepared.receptor_forbidden, None,
                                clash_provider=provider, poses=poses, perturbations=perturbations, radius=radius)
+
+    # ------------------------------------------------------------------ descent in the pose itself (csrc/dlpd_rotate_rgrad.h)
+    @staticmethod
+    def _rodrigues(omega):
+        """exp([omega]x) for omega (n, 3) float64, differentiable at omega = 0 too (the series of sin t / t and
+        (1 - cos t) / t^2 below |omega|^2 = 1e-12)."""
+        t2 = (omega * omega).sum(dim=1)
+        small = t2 < 1e-12
+        t = torch.sqrt(torch.where(small, torch.ones_like(t2), t2))
+        A = torch.where(small, 1.0 - t2 / 6.0, torch.sin(t) / t)
+        B = torch.where(small, 0.5 - t2 / 24.0, (1.0 - torch.cos(t)) / (t * t))
+        z = torch.zeros_like(t2)
+        K = torch.stack([z, -omega[:, 2], omega[:, 1], omega[:, 2], z, -omega[:, 0], -omega[:, 1], omega[:, 0], z], dim=1).reshape(-1, 3, 3)
+        eye = torch.eye(3, dtype=omega.dtype).expand_as(K)
+        return eye + A[:, None, None] * K + B[:, None, None] * torch.matmul(K, K)
+
+    def _pose_objective(self, inputs, clash_provider, base, omega, T, radius):
+        """Score of the states (exp([omega]x) base, T): the minimum of the (2 radius + 1)^3 window of ``_score_poses``'
+        scores -- the same conventions, the correlations from ``ops.local_correlate_rotated(rotation_grad=True)``, the filter
+        CALLED on ``ops.local_features``, the clash mask a constant 0 / 1 factor -- its flat window index (the lowest on a tie)
+        and the gradient of that entry with respect to omega.  -> (score (n), index (n), gradient (n, 3)), float64 on the CPU."""
+        from deeplocalproteindocking_amd import ops
+        model, cv, dev, lib = self.docking_model, self.conventions, self.device, self._lib
+        rec, lig, scale, clip, rf, lf = inputs
+        L, r, n = rec[0].shape[-1], int(radius), omega.shape[0]
+        W = 2 * r + 1
+        batch = max(1, min(n, PROVIDER_BATCH_BYTES // (4 * L ** 3))) if (rf is not None and clash_provider is not None) else n
+        score, index, grad = [], [], []
+        for beg in range(0, n, batch):
+            sl = slice(beg, min(n, beg + batch))
+            w = omega[sl].detach().clone().requires_grad_()
+            with torch.enable_grad():
+                Rb = torch.matmul(self._rodrigues(w), base[sl]).to(device=dev, dtype=torch.float32)
+                Tb = T[sl].to(torch.int32).to(dev).contiguous()
+                corr0 = ops.local_correlate_rotated(rec[0], lig[0], Tb, cv.matrices(Rb, L), radius=r, scale=1, coarse="floor",
+                                                    center=self.rotation_pivot(L), lib=lib, rotation_grad=True)
+                corr1 = None
+                if len(rec) == 2:
+                    L1 = rec[1].shape[-1]
+                    corr1 = ops.local_correlate_rotated(rec[1], lig[1], Tb, cv.matrices(Rb, L1), radius=ops.local_coarse_radius(r, scale),
+                                                        scale=scale, coarse="floor", center=self.rotation_pivot(L1), lib=lib,
+                                                        rotation_grad=True)
+                feat = ops.local_features(corr0, corr1, Tb, r, scale=scale, coarse="floor", clip=clip)
+                V = model.filter(feat).reshape(Rb.shape[0], W ** 3).to(torch.float32)
+                if rf is not None:
+                    with torch.no_grad():
+                        Rd = Rb.detach().contiguous()
+                        if clash_provider is not None:
+                            lfb = clash_provider(Rd).reshape(Rd.shape[0], 1, L, L, L).contiguous()
+                            clash = ops.local_correlate(rf, lfb, Tb, R=None, radius=r, lib=lib)
+                        else:
+                            clash = ops.local_correlate(rf, lf, Tb, R=cv.matrices(Rd, L), radius=r, center=self.rotation_pivot(L), lib=lib)
+                        mask = torch.lt(clash.reshape(Rd.shape[0], W ** 3), model.threshold_clash).to(torch.float32)
+                    V = mask * V
+                Vd = V.detach()
+                low = Vd.min(dim=1, keepdim=True).values
+                ar = torch.arange(W ** 3, device=dev).expand_as(Vd)
+                idx = torch.where(Vd == low, ar, torch.full_like(ar, W ** 3)).min(dim=1).values          # the lowest index on a tie
+                picked = V.gather(1, idx[:, None])
+                (g,) = torch.autograd.grad(picked.sum(), w, allow_unused=True)          # (through that entry only; no parameter's .grad)
+            score.append(picked.detach().reshape(-1).to("cpu", torch.float64))
+            index.append(idx.to("cpu"))
+            grad.append(torch.zeros_like(w) if g is None else g.detach())
+        return torch.cat(score), torch.cat(index), torch.cat(grad)
+
+    def minimize(self, receptor_volumes, ligand_volumes, receptor_forbidden=None, ligand_forbidden=None, clash_provider=None,
+                 poses=None, radius=1, steps=20, max_angle=2.0, min_angle=0.02):
+        """Descent of the score in the rotation itself, for a list of poses (default: ``self.top_list``, which is not touched).
+        Pose (i, x, y, z, score) starts at R0 = rot.R[i] and its signed translation; the state is omega (3, float64, from 0), the
+        rotation exp([omega]x) R0.  The score of a state is the minimum of the (2 radius + 1)^3 window of ``score_poses``'
+        scores round the state's translation (the lowest index on a tie), the translation is recentred on that entry, and the
+        gradient is taken through that entry (``ops.local_correlate_rotated(rotation_grad=True)``; the clash mask is a constant
+        factor).  Per pose: alpha = ``max_angle`` degrees; the trial omega - alpha g / |g| is accepted only if its score is
+        strictly lower, otherwise alpha halves; a pose stops after ``steps`` trials, when alpha < ``min_angle`` or when
+        |g| = 0 (a fully masked window).  All poses advance together; nothing is random.
+        -> ``self.refined_list`` in ``refine``'s format: (R float64 (3, 3), (tx, ty, tz) signed ints, score, position of the source
+        pose in ``poses``), stable-sorted by score; the scores are ``score_poses``' at the final pose, and a pose whose descent
+        did not end strictly below its re-scored source comes back as that source.  Every rank minimises the whole list."""
+        if receptor_forbidden is not None and ligand_forbidden is None and clash_provider is None:
+            raise Exception("minimize: receptor_forbidden needs the ligand's side of the clash channel: ligand_forbidden or clash_provider")
+        poses = list(self.top_list if poses is None else poses)
+        self.refined_list = []
+        if len(poses) == 0:
+            return self.refined_list
+        model = self.docking_model
+        was_training = bool(getattr(model, "training", False))
+        if was_training:
+            model.eval()
+        try:
+            r, W, n = int(radius), 2 * int(radius) + 1, len(poses)
+            inputs = self._pose_inputs(receptor_volumes, ligand_volumes, receptor_forbidden, ligand_forbidden, clash_provider)
+            base = torch.stack([self.rot.R[int(p[0])].to(torch.float64) for p in poses]).cpu()                 # (n, 3, 3)
+            t0 = torch.tensor([self.signed_translation(p[1], p[2], p[3]) for p in poses], dtype=torch.int64)
+
+            def window_offset(idx):
+                return torch.stack([idx // (W * W) - r, (idx // W) % W - r, idx % W - r], dim=1)
+            omega = torch.zeros(n, 3, dtype=torch.float64)
+            f, idx, g = self._pose_objective(inputs, clash_provider, base, omega, t0, r)
+            T = t0 + window_offset(idx)
+            alpha = torch.full((n,), float(np.deg2rad(max_angle)), dtype=torch.float64)
+            floor_, left = float(np.deg2rad(min_angle)), torch.full((n,), int(steps), dtype=torch.int64)
+            while True:
+                norm = g.norm(dim=1)
+                act = torch.nonzero((left > 0) & (alpha >= floor_) & (norm > 0)).reshape(-1)
+                if act.numel() == 0:
+                    break
+                trial = omega[act] - (alpha[act] / norm[act])[:, None] * g[act]
+                ft, it, gt = self._pose_objective(inputs, clash_provider, base[act], trial, T[act], r)
+                ok = ft < f[act]
+                won, lost = act[ok], act[~ok]
+                omega[won], f[won], g[won] = trial[ok], ft[ok], gt[ok]
+                T[won] = T[won] + window_offset(it[ok])
+                alpha[lost] = alpha[lost] * 0.5
+                left[act] -= 1
+            with torch.no_grad():
+                Rfin = torch.matmul(self._rodrigues(omega), base)
+            both = self._score_poses(receptor_volumes, ligand_volumes, torch.cat([base, Rfin]), torch.cat([t0, T]), receptor_forbidden,
+                                     ligand_forbidden, clash_provider, 0).reshape(2, n).cpu().numpy()
+        finally:
+            if was_training:
+                model.train()
+        for k in range(n):
+            if both[1, k] < both[0, k]:
+                self.refined_list.append((Rfin[k].numpy().copy(), tuple(int(v) for v in T[k]), float(both[1, k]), k))
+            else:
+                self.refined_list.append((base[k].numpy().copy(), tuple(int(v) for v in t0[k]), float(both[0, k]), k))
+        self.refined_list.sort(key=lambda e: e[2])
+        return self.refined_list
+
+    def minimize_prepared(self, prepared, radius=1, poses=None, steps=20, max_angle=2.0, min_angle=0.02):
+        """``minimize`` for a target given as files, as ``refine_prepared``: the SE3 ``PreparedPair``'s volumes, the clash channel
+        re-projected from the rotated ligand atoms."""
+        if prepared.group != "SE3":
+            raise Exception("minimize needs the ligand's volumes: SE3 pairs only", prepared.group)
+        be = self._need_backend()
+        L, res, dev = self.box_size, self.resolution, self.device
+        lc, ln, lo = prepared.ligand_atoms
+
+        def provider(Rb):
+            with torch.no_grad():
+                return be.project(lc, ln, lo, L, res, dev, R=Rb, shift=self.box_center, sum_types=True)
+        return self.minimize(prepared.receptor_volumes, prepared.ligand_volumes, prepared.receptor_forbidden, None,
+                             clash_provider=provider, poses=poses, radius=radius, steps=steps, max_angle=max_angle,
+                             min_angle=min_angle)
 
     @property
     def rotation_center(self):

@@ -35,6 +35,8 @@ SIGNATURES = {
     "dlpd_local_filter": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _i, _f, _f, _p, _p, _p, _p]),
     "dlpd_rotate_trilinear": (_i, [_p, _p, _p, _i, _i, _i, _ll, _f, _p]),
     "dlpd_rotate_trilinear_grad": (_i, [_p, _p, _p, _i, _i, _i, _ll, _f, _i, _p]),
+    "dlpd_rotate_trilinear_rgrad_ws_bytes": (_sz, [_i, _i]),
+    "dlpd_rotate_trilinear_rgrad": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _ll, _f, _p]),
     "dlpd_zfft": (_i, [_p, _p, _p, _i, _i, _i, _ll, _i, _f, _p]),
     "dlpd_zfft_into": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _ll, _i, _f, _p]),
     "dlpd_zfft_volumes_occ": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _ll, _i, _p]),

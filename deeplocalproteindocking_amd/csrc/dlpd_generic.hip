@@ -14,6 +14,7 @@
 #include "dlpd_local.h"                 // local docking: direct correlation at given poses (any box size, no plan)
 #include "dlpd_local_grad.h"            // ... and its adjoint (the receptor's and the ligand's gradient)
 #include "dlpd_rotate_grad.h"           // ... and the adjoint of the rotation (the ligand's gradient through the poses)
+#include "dlpd_rotate_rgrad.h"          // ... and the rotation's gradient with respect to its matrix (the poses' own gradient)
 
 #define GEN_MAXN 256                      // box sizes up to 128 (tile: n_in x 64 complex <= 128 KB)
 #define GEN_NACC 4                        // partial sums per output of a direct transform (the final adds are written for 4)

@@ -8,7 +8,9 @@ TorchProteinLibrary's volume ops, backed by libdlpd.so.
 
     VolumeRotation also takes ONE (C,L,L,L) volume set for all B matrices, and is differentiable with respect to the
     volume (csrc/dlpd_rotate_grad.h), as the local correlations below are (local_correlate, local_correlate_rotated,
-    MultiplyVolumes: csrc/dlpd_local_grad.h).  First order; R and T receive no gradient.
+    MultiplyVolumes: csrc/dlpd_local_grad.h).  First order; T receives no gradient, and R only where it is asked for:
+    ``VolumeRotation(rotation_grad=True)`` and ``local_correlate_rotated(..., rotation_grad=True)`` also return the gradient
+    of the rotation matrices (csrc/dlpd_rotate_rgrad.h), what ``Docker.minimize`` descends.
     ``conv3d_autograd`` is the plugins' stride-1 convolution with both gradients on the HIP kernels
     (``conv3d_input_grad``, ``conv3d_weight_grad``: csrc/dlpd_conv_grad.h); plain ``conv3d`` stays inference only.
 
@@ -37,8 +39,9 @@ class VolumeRotation(nn.Module):
     """``center`` / ``scale`` / ``axis_order``: the conventions of Utils/Conventions.py (pivot index; stretch of the
     sample offset -- a number or "(L-1)/L" / "L/(L-1)"; "xyz" | "zyx"), folded into the 3x3 maps the kernel samples with."""
 
-    def __init__(self, center=None, lib=None, scale=None, axis_order="xyz", transpose=False):
+    def __init__(self, center=None, lib=None, scale=None, axis_order="xyz", transpose=False, rotation_grad=False):
         super().__init__()
+        self.rotation_grad = bool(rotation_grad)
         self.center = center
         self.lib = lib
         self.scale = scale
@@ -49,7 +52,10 @@ class VolumeRotation(nn.Module):
         """volume (B, C, L, L, L) with R (B, 3, 3), or ONE (C, L, L, L) volume set for all B matrices -> (B, C, L, L, L).
         Differentiable with respect to ``volume`` (first order; csrc/dlpd_rotate_grad.h): when autograd is enabled and the
         volume requires a gradient the call is recorded -- the shared form's gradient is the sum over the B rotations.  ``R``
-        receives no gradient.  In every other case the call is the plain forward (the same bits either way)."""
+        receives a gradient only from an operator built with ``rotation_grad=True`` (csrc/dlpd_rotate_rgrad.h: the derivative
+        of the trilinear sample, the right-hand one on a cell face; the conventions are folded into the kernel's maps in
+        plain torch, so autograd carries it back to ``R``).  In every other case the call is the plain forward (the same
+        bits either way)."""
         volume, R = _check(volume, "volume", self.lib), _check(R, "R", self.lib)
         if volume.dim() not in (4, 5):
             raise RuntimeError("dlpd: VolumeRotation expects (B, C, L, L, L) or (C, L, L, L), got %s" % (tuple(volume.shape),))
@@ -59,6 +65,8 @@ class VolumeRotation(nn.Module):
         c0 = float(L) / 2.0 if self.center is None else float(self.center)
         if self.scale is not None or self.axis_order != "xyz" or self.transpose:
             R = kernel_matrices(R, rotation_scale(self.scale, L), self.axis_order, self.transpose)
+        if self.rotation_grad and torch.is_grad_enabled() and R.requires_grad:
+            return _VolumeRotate.apply(volume, R, c0, self.lib, True)
         if torch.is_grad_enabled() and volume.requires_grad:
             return _VolumeRotate.apply(volume, R, c0, self.lib)
         return _volume_rotate_forward(volume, R, c0, self.lib)
@@ -74,25 +82,42 @@ def _volume_rotate_forward(volume, M, c0, lib):
 
 
 class _VolumeRotate(torch.autograd.Function):
-    """VolumeRotation under autograd: the forward is the plain call, the backward dlpd_rotate_trilinear_grad with the same maps."""
+    """VolumeRotation under autograd: the forward is the plain call, the backward dlpd_rotate_trilinear_grad with the same maps
+    and, for ``rgrad``, dlpd_rotate_trilinear_rgrad: the gradient of the maps themselves."""
 
     @staticmethod
-    def forward(ctx, volume, M, c0, lib):
-        ctx.save_for_backward(M)
+    def forward(ctx, volume, M, c0, lib, rgrad=False):
+        ctx.save_for_backward(M, *((volume,) if rgrad else ()))
         ctx.args = (tuple(volume.shape), c0, lib)
-        return _volume_rotate_forward(volume.detach(), M, c0, lib)
+        return _volume_rotate_forward(volume.detach(), M.detach(), c0, lib)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        (M,) = ctx.saved_tensors
+        M = ctx.saved_tensors[0]
         shape, c0, lib = ctx.args
+        lib_ = lib or get_lib()
         g = _check(gout, "the gradient", lib)
-        C, L = shape[-4], shape[-1]
-        gvol = torch.empty(shape, dtype=torch.float32, device=g.device)
-        (lib or get_lib()).call("dlpd_rotate_trilinear_grad", _ptr(g), _ptr(M), _ptr(gvol), M.shape[0], C, L,
-                                C * L ** 3 if len(shape) == 5 else 0, c0, 0, _stream(g.device))
-        return gvol, None, None, None
+        B, C, L = M.shape[0], shape[-4], shape[-1]
+        stride = C * L ** 3 if len(shape) == 5 else 0
+        gvol = gM = None
+        if ctx.needs_input_grad[0]:
+            gvol = torch.empty(shape, dtype=torch.float32, device=g.device)
+            lib_.call("dlpd_rotate_trilinear_grad", _ptr(g), _ptr(M), _ptr(gvol), B, C, L, stride, c0, 0, _stream(g.device))
+        if len(ctx.saved_tensors) == 2 and ctx.needs_input_grad[1]:
+            vol = ctx.saved_tensors[1].detach()
+            gM = torch.empty(B, 3, 3, dtype=torch.float32, device=g.device)
+            ws = torch.empty(_rgrad_ws_bytes(lib_, B, L), dtype=torch.uint8, device=g.device)
+            lib_.call("dlpd_rotate_trilinear_rgrad", _ptr(g), _ptr(vol), _ptr(M), _ptr(gM), _ptr(ws), B, C, L, stride, c0,
+                      _stream(g.device))
+        return gvol, gM, None, None, None
+
+
+def _rgrad_ws_bytes(lib_, B, L):
+    n = lib_.call("dlpd_rotate_trilinear_rgrad_ws_bytes", B, L)
+    if n == 0:
+        raise RuntimeError("dlpd: the rotation's gradient supports boxes 2..128 (box %d)" % L)
+    return n
 
 
 class VolumeConvolution(nn.Module):
@@ -543,16 +568,20 @@ class _LocalCorrelate(torch.autograd.Function):
         return grec, glig, None, None, None, None, None, None, None
 
 
-def local_correlate_rotated(receptor, ligand, T, R, radius=0, scale=1, coarse="floor", center=None, lib=None):
+def local_correlate_rotated(receptor, ligand, T, R, radius=0, scale=1, coarse="floor", center=None, lib=None, rotation_grad=False):
     """``local_correlate(receptor, ligand, T, R=R, ...)`` -- the same call, the same bits, no rotated volume in memory --
     differentiable in BOTH volumes: what trains a model on the poses of a search's top list (rotations of one ligand).
     The receptor's gradient is the correlation's adjoint kernel with R (it recomputes the sample).  The ligand's goes in two
     steps: the correlation's adjoint without R writes the gradient of every pose's ROTATED ligand into a workspace of at most
     ``LOCAL_WS_BYTES`` (chunks of poses), and the rotation's adjoint (csrc/dlpd_rotate_grad.h) carries each chunk back through
-    its rotations -- summed over the poses, in pose order, for a ligand shared by all of them.  First order; ``T`` and ``R``
-    receive no gradient."""
+    its rotations -- summed over the poses, in pose order, for a ligand shared by all of them.  First order; ``T`` receives
+    no gradient, and ``R`` only with ``rotation_grad=True``: the same workspace contracted with the derivative of the trilinear
+    sample (csrc/dlpd_rotate_rgrad.h) gives the nine numbers of every pose, each from one kernel call -- chunking does not
+    change their bits."""
     if R is None:
         raise RuntimeError("dlpd: local_correlate_rotated needs the rotations R (without them: local_correlate)")
+    if rotation_grad and torch.is_grad_enabled() and R.requires_grad:
+        return _LocalCorrelateRotated.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib, True)
     if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in (receptor, ligand)):
         return _LocalCorrelateRotated.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib)
     return _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib)
@@ -564,26 +593,27 @@ class _LocalCorrelateRotated(torch.autograd.Function):
     (``accumulate``): the chunked result has the bits of the unsplit one."""
 
     @staticmethod
-    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib):
+    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib, rgrad=False):
         ctx.save_for_backward(receptor, ligand, T, R)
-        ctx.args = (radius, scale, coarse, center, lib)
-        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R, radius, scale, coarse, center, lib)
+        ctx.args = (radius, scale, coarse, center, lib, rgrad)
+        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R.detach(), radius, scale, coarse, center, lib)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gcorr):
         receptor, ligand, T, R = ctx.saved_tensors
-        r, scale, coarse, center, lib = ctx.args
+        r, scale, coarse, center, lib, rgrad = ctx.args
         lib_ = lib or get_lib()
         T = T.contiguous()
         P = T.shape[0]
         rec, rs = _pose_volumes(receptor.detach(), P, "receptor", lib)
         lig, ls = _pose_volumes(ligand.detach(), P, "ligand", lib)
-        R = _check(R, "R", lib)
+        R = _check(R.detach(), "R", lib)
         g = _check(gcorr, "the gradient", lib)
         C, L, W = rec.shape[-4], rec.shape[-1], 2 * r + 1
         vol = C * L ** 3
-        want_rec, want_lig = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_rec, want_lig, want_R = ctx.needs_input_grad[0], ctx.needs_input_grad[1], rgrad and ctx.needs_input_grad[3]
+        gR = torch.empty(P, 3, 3, dtype=torch.float32, device=rec.device) if want_R else None
         grec = torch.empty_like(rec) if want_rec else None
         glig = torch.empty_like(lig) if want_lig else None
         c0 = float(L) / 2.0 if center is None else float(center)
@@ -598,15 +628,21 @@ class _LocalCorrelateRotated(torch.autograd.Function):
             step = most if rs != 0 else P             # a gradient per pose: one launch's poses; a shared receptor: all in one call
             for beg in range(0, P, step):
                 run(_ptr(R) + 36 * beg, _ptr(grec) + 4 * rs * beg, None, ls, beg, min(step, P - beg))
-        if want_lig:
+        if want_lig or want_R:
             chunk = max(1, min(P, LOCAL_WS_BYTES // (4 * vol), most))
             ws = torch.empty(chunk * vol, dtype=torch.float32, device=rec.device)
+            if want_R:
+                ws_r = torch.empty(_rgrad_ws_bytes(lib_, chunk, L), dtype=torch.uint8, device=rec.device)
             for beg in range(0, P, chunk):
                 n = min(chunk, P - beg)
                 run(None, None, _ptr(ws), vol, beg, n)             # the gradient of each pose's rotated ligand (no ligand is read)
-                lib_.call("dlpd_rotate_trilinear_grad", _ptr(ws), _ptr(R) + 36 * beg, _ptr(glig) + 4 * ls * beg, n, C, L, ls, c0,
-                          1 if (ls == 0 and beg > 0) else 0, st)
-        return grec, glig, None, None, None, None, None, None, None
+                if want_lig:
+                    lib_.call("dlpd_rotate_trilinear_grad", _ptr(ws), _ptr(R) + 36 * beg, _ptr(glig) + 4 * ls * beg, n, C, L, ls,
+                              c0, 1 if (ls == 0 and beg > 0) else 0, st)
+                if want_R:                                         # ... contracted with the sample's derivative: 9 numbers per pose
+                    lib_.call("dlpd_rotate_trilinear_rgrad", _ptr(ws), _ptr(lig) + 4 * ls * beg, _ptr(R) + 36 * beg,
+                              _ptr(gR) + 36 * beg, _ptr(ws_r), n, C, L, ls, c0, st)
+        return grec, glig, None, gR, None, None, None, None, None, None
 
 
 def local_coarse_radius(radius, scale):

@@ -76,6 +76,18 @@ int dlpd_rotate_trilinear(const float* vol, const float* R, float* out, int B, i
  * Null pointers, B or C <= 0 or a negative stride: DLPD_ERR_ARG; L < 2 or L > 128: DLPD_ERR_UNSUPPORTED. */
 int dlpd_rotate_trilinear_grad(const float* gout, const float* R, float* gvol, int B, int C, int L, long long gvol_bstride,
                                float center, int accumulate, void* stream);
+/* The gradient of that call with respect to the MATRICES (what a descent of a docking score in the pose itself needs):
+ *   gR[b][3j + a] = sum_c sum_i gout[b,c](i) * d_a vol[b,c]( p_b(i) ) * (i_j - center),
+ *   p_a(i) = center + sum_j R[b][3j + a] (i_j - center) the forward's sample position, d_a the derivative of the trilinear
+ *   sample along axis a: the same floor, in-box masks and corners as the forward (on a cell face: the right-hand derivative).
+ * gout (B,C,L^3); vol, R, vol_bstride and center as the forward took them; gR (B,9) laid out as R, every element written.
+ * Per voxel the sum over the channels is a float32 chain, everything after it float64: block partials go to ws
+ * (dlpd_rotate_trilinear_rgrad_ws_bytes(B, L) bytes; 0 for an unsupported shape) and are added in block order -- no atomics,
+ * the same bits run to run, and a pose's nine numbers do not depend on the other poses of its call.
+ * Null pointers, B or C <= 0 or a negative stride: DLPD_ERR_ARG; L < 2 or L > 128: DLPD_ERR_UNSUPPORTED. */
+size_t dlpd_rotate_trilinear_rgrad_ws_bytes(int B, int L);
+int dlpd_rotate_trilinear_rgrad(const float* gout, const float* vol, const float* R, float* gR, void* ws, int B, int C, int L,
+                                long long vol_bstride, float center, void* stream);
 
 /* Stage K1 of TPL VolumeConvolution (src/Models/DockingModels.py:71, src/Docker/Docker.py:225),
  * optionally fused with the rotation of Docker.py:218: z-axis R2C of (rotated) volumes.

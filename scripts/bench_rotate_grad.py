@@ -9,6 +9,11 @@ LocalDockingModel.forward_poses step (forward + backward).  Prints one JSON line
     python scripts/bench_rotate_grad.py --counters prof/rotate_grad_pmc      # + hardware counters of the adjoint kernel, in
                                                                              #   a run of their own (no tracing beside them)
     python scripts/bench_rotate_grad.py --kernel-only | --step-only          # what those children run
+    python scripts/bench_rotate_grad.py --pose-grad [--minimize-poses 32]    # the rotation's gradient with respect to its
+                                                                             #   matrices (csrc/dlpd_rotate_rgrad.h): the backward
+                                                                             #   of local_correlate_rotated with and without
+                                                                             #   rotation_grad, the new kernel beside the adjoint on
+                                                                             #   one workspace, Docker.minimize beside Docker.refine
 
 The adjoint's floor is memory traffic: it reads B C L^3 4 bytes (the gradient of every rotated copy) and writes C L^3 4.
 Needs a GPU: no CPU fallback."""
@@ -108,6 +113,92 @@ def model_step(dev, P):
     return step
 
 
+def pose_grad_rows(lib, dev, P, repeats, variants=()):
+    """Per shape: the backward of ops.local_correlate_rotated (radius 1, one shared ligand) with rotation_grad=True against the
+    same call without it, and dlpd_rotate_trilinear_rgrad beside dlpd_rotate_trilinear_grad on the same workspace."""
+    from deeplocalproteindocking_amd import ops
+    from deeplocalproteindocking_amd.engine import _stream
+    R = rotations(P).to(dev)
+    g_ = torch.Generator().manual_seed(6)
+    T = torch.from_numpy(np.random.RandomState(9).randint(-10, 11, size=(P, 3))).int().to(dev)
+    for C, L in SHAPES:
+        rec, lig = torch.randn(C, L, L, L, generator=g_).to(dev), torch.randn(C, L, L, L, generator=g_).to(dev)
+        gcorr = torch.randn(P, C, 3, 3, 3, generator=g_).to(dev)
+        row = {"part": "pose gradient %d @ %d^3, %d poses of one ligand, radius 1 (device events)" % (C, L, P)}
+        for name, flag in (("backward_ms", False), ("backward_rotation_grad_ms", True), ("backward_ms_again", False),
+                           ("backward_rotation_grad_ms_again", True)):
+            a, b, Rg = rec.clone().requires_grad_(), lig.clone().requires_grad_(), R.clone().requires_grad_()
+            out = ops.local_correlate_rotated(a, b, T, Rg, radius=1, rotation_grad=flag)
+            row[name] = _timed(lambda: torch.autograd.grad(out, (a, b, Rg) if flag else (a, b), gcorr, retain_graph=True), repeats)
+        ws = torch.randn(P, C, L, L, L, generator=g_).to(dev)
+        gvol, gR = torch.empty_like(lig), torch.empty(P, 9, device=dev)
+        part = torch.empty(lib.call("dlpd_rotate_trilinear_rgrad_ws_bytes", P, L), dtype=torch.uint8, device=dev)
+        st, c0 = _stream(dev), L / 2.0
+        row["k_rotate_adjoint_ms"] = _timed(lambda: lib.call("dlpd_rotate_trilinear_grad", ws.data_ptr(), R.data_ptr(), gvol.data_ptr(),
+                                                             P, C, L, 0, c0, 0, st), repeats)
+        row["k_rotate_rgrad_ms"] = _timed(lambda: lib.call("dlpd_rotate_trilinear_rgrad", ws.data_ptr(), lig.data_ptr(), R.data_ptr(),
+                                                           gR.data_ptr(), part.data_ptr(), P, C, L, 0, c0, st), repeats)
+        row["k_rotate_adjoint_us_per_pose"] = 1e3 * row["k_rotate_adjoint_ms"]["median"] / P
+        row["k_rotate_rgrad_us_per_pose"] = 1e3 * row["k_rotate_rgrad_ms"]["median"] / P
+        row["rgrad_floor_bytes"] = (P + 1) * C * L ** 3 * 4
+        row["rgrad_achieved_TB_per_s"] = row["rgrad_floor_bytes"] / (row["k_rotate_rgrad_ms"]["median"] * 1e-3) / 1e12
+        print(json.dumps(row), flush=True)
+        if variants:                                          # A/B builds of the kernel: every library twice, alternating
+            row = {"part": "k_rotate_rgrad variants %d @ %d^3, %d poses (device events, alternating)" % (C, L, P)}
+            for rnd in range(2):
+                for name, l in [("product", lib)] + list(variants):
+                    pv = torch.empty(l.call("dlpd_rotate_trilinear_rgrad_ws_bytes", P, L), dtype=torch.uint8, device=dev)
+                    row["%s_ms_round%d" % (name, rnd)] = _timed(lambda: l.call(
+                        "dlpd_rotate_trilinear_rgrad", ws.data_ptr(), lig.data_ptr(), R.data_ptr(), gR.data_ptr(), pv.data_ptr(), P, C, L,
+                        0, c0, st), repeats)["median"]
+            print(json.dumps(row), flush=True)
+        del ws, rec, lig
+
+
+def minimize_row(dev, npose, steps=20, rounds=3):
+    """Docker.minimize(steps) beside Docker.refine (default perturbations) on the top ``npose`` poses of a short search over
+    bench.py's real_protein volumes: wall time per pose (``rounds`` times each, alternating, after one warm-up) and scores."""
+    import time
+    import bench
+    from deeplocalproteindocking_amd.Docker import Docker
+    from deeplocalproteindocking_amd.Models import GlobalDockingModel, SimpleFilter
+    from deeplocalproteindocking_amd.Utils.Rotations import Rotations
+    L = 80
+    rec, lig, recf, ligf = bench.protein_pair_volumes(dev, L)
+    thr = bench.clash_threshold(recf, ligf)
+    torch.manual_seed(1)
+    filt = SimpleFilter([rec[0].shape[0], rec[1].shape[0]])
+    with torch.no_grad():                                 # a pose without contact scores 0, as in bench.py's real_protein
+        W1, b1, W2, b2 = filt.parameters_tuple()
+        filt.fc[2].bias -= float((W2.reshape(1, -1) @ torch.relu(b1.reshape(-1, 1))).reshape(-1)[0] + b2.reshape(-1)[0])
+    model = GlobalDockingModel(None, filt, threshold_clash=thr).to(dev).eval()
+    rot = Rotations(angle_inc=15, allow_generated=True, verbose=False)
+    dk = Docker(model, box_size=L, max_conf=npose, rotations=rot.R.numpy()[:256], device=dev)
+    with torch.no_grad():
+        top = list(dk.dock_volumes(rec, lig, recf, ligf, write=False))
+    dk.release_engine()
+    calls = {"refine": lambda: dk.refine(rec, lig, recf, ligf, poses=top), "minimize": lambda: dk.minimize(rec, lig, recf, ligf, poses=top, steps=steps)}
+    ms, lists = {"refine": [], "minimize": []}, {}
+    for rnd in range(rounds + 1):
+        for name, fn in calls.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lists[name] = list(fn())
+            torch.cuda.synchronize()
+            if rnd > 0:
+                ms[name].append(1e3 * (time.perf_counter() - t0) / len(top))
+    row = {"part": "Docker.minimize(steps=%d) beside Docker.refine(5 degrees, 1), %d poses of a 256-rotation search, real_protein "
+                   "volumes [16 @ 80^3, 32 @ 40^3] (wall time)" % (steps, len(top)), "search_scores": [top[0][4], float(np.mean([t[4] for t in top]))]}
+    for name in calls:
+        sc = [e[2] for e in lists[name]]
+        row[name] = {"ms_per_pose": {"median": float(np.median(ms[name])), "min": min(ms[name]), "max": max(ms[name])},
+                     "best_score": min(sc), "mean_score": float(np.mean(sc)),
+                     "improved": int(sum(e[2] < top[e[3]][4] for e in lists[name]))}
+    by = {e[3]: e[2] for e in lists["refine"]}
+    row["minimize_below_refine"] = int(sum(e[2] < by[e[3]] for e in lists["minimize"]))
+    print(json.dumps(row), flush=True)
+
+
 def _stats(directory):
     files = glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True)
     assert files, "rocprofv3 wrote no kernel statistics under %s" % directory
@@ -128,8 +219,11 @@ def main():
     ap.add_argument("--adjoint-only", action="store_true")
     ap.add_argument("--step-only", action="store_true")
     ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--pose-grad", action="store_true", help="only the rows of the rotation's gradient with respect to its matrices")
+    ap.add_argument("--minimize-poses", type=int, default=32)
     ap.add_argument("--variants", default="", help="name=library,... : A/B builds of the adjoint kernel (scripts/build_variant.py "
-                    "NAME --generic=-DDLPD_ROT_GRAD_CC=8 | -DDLPD_ROT_GRAD_SKIP=0), timed beside the product library")
+                    "NAME --generic=-DDLPD_ROT_GRAD_CC=8 | -DDLPD_ROT_GRAD_SKIP=0; with --pose-grad: -DDLPD_ROT_RGRAD_VT=1 | 2 | 8), "
+                    "timed beside the product library")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_rotate_grad.py needs a GPU"
     entry.build()
@@ -140,6 +234,14 @@ def main():
         for _ in range(2 + STEPS):
             step()
         torch.cuda.synchronize()
+        return
+    if args.pose_grad:
+        from deeplocalproteindocking_amd._lib import DlpdLib
+        pose_grad_rows(lib, dev, P, args.repeats,
+                       [(nv.split("=")[0], DlpdLib(nv.split("=")[1])) for nv in args.variants.split(",") if nv])
+        torch.cuda.empty_cache()
+        if args.minimize_poses > 0:
+            minimize_row(dev, args.minimize_poses)
         return
     ks = kernels(lib, dev, P)
     if args.kernel_only or args.adjoint_only:
