@@ -361,13 +361,18 @@ class Docker:
 
     # ------------------------------------------------------------------ local docking: given poses (csrc/dlpd_local.h)
     def score_poses(self, receptor_volumes, ligand_volumes, R, T, receptor_forbidden=None, ligand_forbidden=None,
-                    clash_provider=None, radius=0):
+                    clash_provider=None, radius=0, shift=None):
         """Scores of GIVEN poses by direct correlation: (P, W, W, W) float32 on ``self.device``, W = 2 radius + 1; entry
         [p, dx, dy, dz] is the pose (R[p], T[p] + (dx, dy, dz) - radius).  R (P, 3, 3) rotation matrices, T (P, 3) signed integer
         translations in fine-grid voxels, |t| < box_size.  The GLOBAL search's conventions throughout -- this Docker's rotation
         conventions, the model's clip and clash threshold, floor(t / 2) on the coarse grid -- so a pose of ``top_list`` gets the
         score the search gave it: ``score_poses(rot.R[i], signed (x, y, z))[0, 0, 0, 0]``.  The volumes and the clash
-        arguments are ``dock_volumes``'s.  Poses are processed in batches sized from the kernel's workspace."""
+        arguments are ``dock_volumes``'s.  Poses are processed in batches sized from the kernel's workspace.
+        ``shift`` (P, 3) float, fine-grid voxels: a fraction of a voxel added to ``T`` -- the ligand is resampled at the displaced
+        position inside the correlation's own trilinear gather (csrc/dlpd_rotate_shift.h).  The coarse resolution gets
+        ``shift / scale`` on top of its floor(t / scale), and a stored ``ligand_forbidden`` is displaced the same way.  With a
+        ``clash_provider`` the clash mask is taken at the WHOLE-voxel translation ``T``: the provider's signature has no
+        translation, its volumes cannot be displaced by a fraction.  Zeros give the bits of the call without ``shift``."""
         model = self.docking_model
         if receptor_forbidden is not None and ligand_forbidden is None and clash_provider is None:
             raise Exception("score_poses: receptor_forbidden needs the ligand's side of the clash channel: ligand_forbidden or clash_provider")
@@ -376,7 +381,8 @@ class Docker:
         if was_training:
             model.eval()
         try:
-            return self._score_poses(receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius)
+            return self._score_poses(receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius,
+                                     shift)
         finally:
             if was_training:
                 model.train()
@@ -410,7 +416,8 @@ class Docker:
                 lf = torch.as_tensor(ligand_forbidden, dtype=torch.float32).reshape(1, L, L, L).to(dev).contiguous()
         return rec, lig, scale, clip, rf, lf
 
-    def _score_poses(self, receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius):
+    def _score_poses(self, receptor_volumes, ligand_volumes, R, T, receptor_forbidden, ligand_forbidden, clash_provider, radius,
+                     shift=None):
         from deeplocalproteindocking_amd import ops
         model = self.docking_model
         dev, lib = self.device, self._lib
@@ -425,6 +432,12 @@ class Docker:
             raise Exception("score_poses: one translation per rotation", T.shape[0], P)
         Td = T.to(torch.int32).to(dev).contiguous()
         Rf = R.to(device=dev, dtype=torch.float32).contiguous()
+        Sf = None
+        if shift is not None:
+            Sf = torch.as_tensor(np.asarray(shift, dtype=np.float64) if not torch.is_tensor(shift) else shift).reshape(-1, 3)
+            if Sf.shape[0] != P:
+                raise Exception("score_poses: one shift per pose", Sf.shape[0], P)
+            Sf = Sf.to(device=dev, dtype=torch.float32).contiguous()
         has_clash = rf is not None
         params = fused_filter_parameters(model)
         W = 2 * r + 1
@@ -434,20 +447,23 @@ class Docker:
         for beg in range(0, P, batch):
             sl = slice(beg, min(P, beg + batch))
             Rb, Tb = Rf[sl], Td[sl]
+            Sb = None if Sf is None else Sf[sl]
             corr0 = ops.local_correlate(rec[0], lig[0], Tb, R=cv.matrices(Rb, L), radius=r, scale=1, coarse="floor",
-                                        center=self.rotation_pivot(L), lib=lib)
+                                        center=self.rotation_pivot(L), lib=lib, shift=Sb)
             corr1 = None
             if len(rec) == 2:
                 L1 = rec[1].shape[-1]
                 corr1 = ops.local_correlate(rec[1], lig[1], Tb, R=cv.matrices(Rb, L1), radius=ops.local_coarse_radius(r, scale), scale=scale,
-                                            coarse="floor", center=self.rotation_pivot(L1), lib=lib)
+                                            coarse="floor", center=self.rotation_pivot(L1), lib=lib,
+                                            shift=None if Sb is None else Sb / float(scale))
             clash = None
             if has_clash:
                 if clash_provider is not None:
                     lfb = clash_provider(Rb).reshape(Rb.shape[0], 1, L, L, L).contiguous()
                     clash = ops.local_correlate(rf, lfb, Tb, R=None, radius=r, lib=lib)
                 else:
-                    clash = ops.local_correlate(rf, lf, Tb, R=cv.matrices(Rb, L), radius=r, center=self.rotation_pivot(L), lib=lib)
+                    clash = ops.local_correlate(rf, lf, Tb, R=cv.matrices(Rb, L), radius=r, center=self.rotation_pivot(L), lib=lib,
+                                                shift=Sb)
                 clash = clash.reshape(Rb.shape[0], W, W, W)
             res = None
             if params is not None:
@@ -551,32 +567,36 @@ class Docker:
         eye = torch.eye(3, dtype=omega.dtype).expand_as(K)
         return eye + A[:, None, None] * K + B[:, None, None] * torch.matmul(K, K)
 
-    def _pose_objective(self, inputs, clash_provider, base, omega, T, radius):
+    def _pose_objective(self, inputs, clash_provider, base, omega, T, radius, shift=None):
         """Score of the states (exp([omega]x) base, T): the minimum of the (2 radius + 1)^3 window of ``_score_poses``'
         scores -- the same conventions, the correlations from ``ops.local_correlate_rotated(rotation_grad=True)``, the filter
         CALLED on ``ops.local_features``, the clash mask a constant 0 / 1 factor -- its flat window index (the lowest on a tie)
-        and the gradient of that entry with respect to omega.  -> (score (n), index (n), gradient (n, 3)), float64 on the CPU."""
+        and the gradient of that entry with respect to omega.  -> (score (n), index (n), gradient (n, 3)), float64 on the CPU.
+        ``shift`` (n, 3) float64, fine-grid voxels (``minimize(translation=True)``): the states are (exp([omega]x) base, T + shift),
+        and a fourth result is the gradient of the same entry with respect to ``shift``."""
         from deeplocalproteindocking_amd import ops
         model, cv, dev, lib = self.docking_model, self.conventions, self.device, self._lib
         rec, lig, scale, clip, rf, lf = inputs
         L, r, n = rec[0].shape[-1], int(radius), omega.shape[0]
         W = 2 * r + 1
         batch = max(1, min(n, PROVIDER_BATCH_BYTES // (4 * L ** 3))) if (rf is not None and clash_provider is not None) else n
-        score, index, grad = [], [], []
+        score, index, grad, gshift = [], [], [], []
         for beg in range(0, n, batch):
             sl = slice(beg, min(n, beg + batch))
             w = omega[sl].detach().clone().requires_grad_()
+            sv = None if shift is None else shift[sl].detach().clone().requires_grad_()
             with torch.enable_grad():
                 Rb = torch.matmul(self._rodrigues(w), base[sl]).to(device=dev, dtype=torch.float32)
                 Tb = T[sl].to(torch.int32).to(dev).contiguous()
+                Sb = None if sv is None else sv.to(device=dev, dtype=torch.float32)
                 corr0 = ops.local_correlate_rotated(rec[0], lig[0], Tb, cv.matrices(Rb, L), radius=r, scale=1, coarse="floor",
-                                                    center=self.rotation_pivot(L), lib=lib, rotation_grad=True)
+                                                    center=self.rotation_pivot(L), lib=lib, rotation_grad=True, shift=Sb)
                 corr1 = None
                 if len(rec) == 2:
                     L1 = rec[1].shape[-1]
                     corr1 = ops.local_correlate_rotated(rec[1], lig[1], Tb, cv.matrices(Rb, L1), radius=ops.local_coarse_radius(r, scale),
                                                         scale=scale, coarse="floor", center=self.rotation_pivot(L1), lib=lib,
-                                                        rotation_grad=True)
+                                                        rotation_grad=True, shift=None if Sb is None else Sb / float(scale))
                 feat = ops.local_features(corr0, corr1, Tb, r, scale=scale, coarse="floor", clip=clip)
                 V = model.filter(feat).reshape(Rb.shape[0], W ** 3).to(torch.float32)
                 if rf is not None:
@@ -586,7 +606,8 @@ class Docker:
                             lfb = clash_provider(Rd).reshape(Rd.shape[0], 1, L, L, L).contiguous()
                             clash = ops.local_correlate(rf, lfb, Tb, R=None, radius=r, lib=lib)
                         else:
-                            clash = ops.local_correlate(rf, lf, Tb, R=cv.matrices(Rd, L), radius=r, center=self.rotation_pivot(L), lib=lib)
+                            clash = ops.local_correlate(rf, lf, Tb, R=cv.matrices(Rd, L), radius=r, center=self.rotation_pivot(L), lib=lib,
+                                                        shift=None if Sb is None else Sb.detach())
                         mask = torch.lt(clash.reshape(Rd.shape[0], W ** 3), model.threshold_clash).to(torch.float32)
                     V = mask * V
                 Vd = V.detach()
@@ -594,14 +615,20 @@ class Docker:
                 ar = torch.arange(W ** 3, device=dev).expand_as(Vd)
                 idx = torch.where(Vd == low, ar, torch.full_like(ar, W ** 3)).min(dim=1).values          # the lowest index on a tie
                 picked = V.gather(1, idx[:, None])
-                (g,) = torch.autograd.grad(picked.sum(), w, allow_unused=True)          # (through that entry only; no parameter's .grad)
+                if sv is None:
+                    (g,) = torch.autograd.grad(picked.sum(), w, allow_unused=True)      # (through that entry only; no parameter's .grad)
+                else:
+                    g, gs = torch.autograd.grad(picked.sum(), (w, sv), allow_unused=True)
+                    gshift.append(torch.zeros_like(sv) if gs is None else gs.detach())
             score.append(picked.detach().reshape(-1).to("cpu", torch.float64))
             index.append(idx.to("cpu"))
             grad.append(torch.zeros_like(w) if g is None else g.detach())
+        if shift is not None:
+            return torch.cat(score), torch.cat(index), torch.cat(grad), torch.cat(gshift)
         return torch.cat(score), torch.cat(index), torch.cat(grad)
 
     def minimize(self, receptor_volumes, ligand_volumes, receptor_forbidden=None, ligand_forbidden=None, clash_provider=None,
-                 poses=None, radius=1, steps=20, max_angle=2.0, min_angle=0.02):
+                 poses=None, radius=1, steps=20, max_angle=2.0, min_angle=0.02, translation=False, lever=None):
         """Descent of the score in the rotation itself, for a list of poses (default: ``self.top_list``, which is not touched).
         Pose (i, x, y, z, score) starts at R0 = rot.R[i] and its signed translation; the state is omega (3, float64, from 0), the
         rotation exp([omega]x) R0.  The score of a state is the minimum of the (2 radius + 1)^3 window of ``score_poses``'
@@ -612,7 +639,18 @@ class Docker:
         |g| = 0 (a fully masked window).  All poses advance together; nothing is random.
         -> ``self.refined_list`` in ``refine``'s format: (R float64 (3, 3), (tx, ty, tz) signed ints, score, position of the source
         pose in ``poses``), stable-sorted by score; the scores are ``score_poses``' at the final pose, and a pose whose descent
-        did not end strictly below its re-scored source comes back as that source.  Every rank minimises the whole list."""
+        did not end strictly below its re-scored source comes back as that source.  Every rank minimises the whole list.
+        ``translation=True``: a rigid-body descent -- the state is (omega, s), s (3, float64, from 0) a FRACTION of a fine-grid voxel
+        added to the translation (``score_poses(shift=)``; csrc/dlpd_rotate_shift.h), and the gradient is taken through the picked
+        window entry with respect to both.  Steps are taken in the scaled coordinates (lever * omega, s), ``lever`` in voxels
+        (default box_size / 4: a rotation by theta counts as lever * theta voxels): the trial step has length alpha * lever along
+        the normalised scaled gradient; accept / halve / stop as above.  After an accepted step the whole voxels of s move into
+        the integer translation (s stays in [-0.5, 0.5]).  Entries carry the translation as three FLOATS T + s, which
+        ``split_translation`` takes apart again, and the scores are ``score_poses(R, T, shift=s)``' own.  With a ``clash_provider``
+        the mask is the whole-voxel one (``score_poses``).  ``translation=False`` is the descent above, ints included."""
+        if translation:
+            return self._minimize_rigid(receptor_volumes, ligand_volumes, receptor_forbidden, ligand_forbidden, clash_provider, poses,
+                                        radius, steps, max_angle, min_angle, lever)
         if receptor_forbidden is not None and ligand_forbidden is None and clash_provider is None:
             raise Exception("minimize: receptor_forbidden needs the ligand's side of the clash channel: ligand_forbidden or clash_provider")
         poses = list(self.top_list if poses is None else poses)
@@ -664,9 +702,85 @@ class Docker:
         self.refined_list.sort(key=lambda e: e[2])
         return self.refined_list
 
-    def minimize_prepared(self, prepared, radius=1, poses=None, steps=20, max_angle=2.0, min_angle=0.02):
+    @staticmethod
+    def split_translation(tt):
+        """A translation of ``minimize(translation=True)``'s list, three floats -> (the whole voxels T = floor(t + 1/2) as ints,
+        the fractions s = t - T in [-0.5, 0.5) as floats): the (T, shift) ``score_poses`` takes.  The subtraction is exact in
+        float64, so the split of a list entry is the split its score was computed with."""
+        T = [int(np.floor(float(v) + 0.5)) for v in tt]
+        return tuple(T), tuple(float(v) - k for v, k in zip(tt, T))
+
+    def _minimize_rigid(self, receptor_volumes, ligand_volumes, receptor_forbidden, ligand_forbidden, clash_provider, poses, radius,
+                        steps, max_angle, min_angle, lever):
+        """``minimize(translation=True)`` (its docstring)."""
+        if receptor_forbidden is not None and ligand_forbidden is None and clash_provider is None:
+            raise Exception("minimize: receptor_forbidden needs the ligand's side of the clash channel: ligand_forbidden or clash_provider")
+        poses = list(self.top_list if poses is None else poses)
+        self.refined_list = []
+        if len(poses) == 0:
+            return self.refined_list
+        lever = float(self.box_size) / 4.0 if lever is None else float(lever)
+        if not lever > 0:
+            raise Exception("minimize: lever must be positive (voxels)", lever)
+        model = self.docking_model
+        was_training = bool(getattr(model, "training", False))
+        if was_training:
+            model.eval()
+        try:
+            r, W, n = int(radius), 2 * int(radius) + 1, len(poses)
+            inputs = self._pose_inputs(receptor_volumes, ligand_volumes, receptor_forbidden, ligand_forbidden, clash_provider)
+            base = torch.stack([self.rot.R[int(p[0])].to(torch.float64) for p in poses]).cpu()                 # (n, 3, 3)
+            t0 = torch.tensor([self.signed_translation(p[1], p[2], p[3]) for p in poses], dtype=torch.int64)
+
+            def window_offset(idx):
+                return torch.stack([idx // (W * W) - r, (idx // W) % W - r, idx % W - r], dim=1)
+            omega, s = torch.zeros(n, 3, dtype=torch.float64), torch.zeros(n, 3, dtype=torch.float64)
+            f, idx, g, gs = self._pose_objective(inputs, clash_provider, base, omega, t0, r, shift=s)
+            T = t0 + window_offset(idx)
+            alpha = torch.full((n,), float(np.deg2rad(max_angle)), dtype=torch.float64)
+            floor_, left = float(np.deg2rad(min_angle)), torch.full((n,), int(steps), dtype=torch.int64)
+            while True:
+                # the gradient in the scaled coordinates (lever * omega, s)
+                norm = torch.sqrt((g * g).sum(dim=1) / lever ** 2 + (gs * gs).sum(dim=1))
+                act = torch.nonzero((left > 0) & (alpha >= floor_) & (norm > 0)).reshape(-1)
+                if act.numel() == 0:
+                    break
+                step = (alpha[act] * lever / norm[act])[:, None]                        # a step of length alpha * lever (voxels)
+                trial_w = omega[act] - step * g[act] / lever ** 2
+                trial_s = s[act] - step * gs[act]
+                ft, it, gt, gst = self._pose_objective(inputs, clash_provider, base[act], trial_w, T[act], r, shift=trial_s)
+                ok = ft < f[act]
+                won, lost = act[ok], act[~ok]
+                omega[won], f[won], g[won], gs[won] = trial_w[ok], ft[ok], gt[ok], gst[ok]
+                whole = torch.floor(trial_s[ok] + 0.5)                                  # whole voxels of s move into T
+                s[won] = trial_s[ok] - whole
+                T[won] = T[won] + window_offset(it[ok]) + whole.to(torch.int64)
+                alpha[lost] = alpha[lost] * 0.5
+                left[act] -= 1
+            with torch.no_grad():
+                Rfin = torch.matmul(self._rodrigues(omega), base)
+            # the list's translation is T + s as floats; its score is that of the split split_translation returns
+            tt = (T.to(torch.float64) + s).numpy()
+            split = [self.split_translation(row) for row in tt]
+            Tn = torch.tensor([k for k, _ in split], dtype=torch.int64).reshape(n, 3)
+            sn = torch.tensor([q for _, q in split], dtype=torch.float64).reshape(n, 3)
+            both = self._score_poses(receptor_volumes, ligand_volumes, torch.cat([base, Rfin]), torch.cat([t0, Tn]), receptor_forbidden,
+                                     ligand_forbidden, clash_provider, 0, shift=torch.cat([torch.zeros_like(sn), sn]))
+            both = both.reshape(2, n).cpu().numpy()
+        finally:
+            if was_training:
+                model.train()
+        for k in range(n):
+            if both[1, k] < both[0, k]:
+                self.refined_list.append((Rfin[k].numpy().copy(), tuple(float(v) for v in tt[k]), float(both[1, k]), k))
+            else:
+                self.refined_list.append((base[k].numpy().copy(), tuple(float(v) for v in t0[k]), float(both[0, k]), k))
+        self.refined_list.sort(key=lambda e: e[2])
+        return self.refined_list
+
+    def minimize_prepared(self, prepared, radius=1, poses=None, steps=20, max_angle=2.0, min_angle=0.02, translation=False, lever=None):
         """``minimize`` for a target given as files, as ``refine_prepared``: the SE3 ``PreparedPair``'s volumes, the clash channel
-        re-projected from the rotated ligand atoms."""
+        re-projected from the rotated ligand atoms (with ``translation=True``: at the whole-voxel translation)."""
         if prepared.group != "SE3":
             raise Exception("minimize needs the ligand's volumes: SE3 pairs only", prepared.group)
         be = self._need_backend()
@@ -678,7 +792,7 @@ class Docker:
                 return be.project(lc, ln, lo, L, res, dev, R=Rb, shift=self.box_center, sum_types=True)
         return self.minimize(prepared.receptor_volumes, prepared.ligand_volumes, prepared.receptor_forbidden, None,
                              clash_provider=provider, poses=poses, radius=radius, steps=steps, max_angle=max_angle,
-                             min_angle=min_angle)
+                             min_angle=min_angle, translation=translation, lever=lever)
 
     @property
     def rotation_center(self):

@@ -37,6 +37,12 @@ SIGNATURES = {
     "dlpd_rotate_trilinear_grad": (_i, [_p, _p, _p, _i, _i, _i, _ll, _f, _i, _p]),
     "dlpd_rotate_trilinear_rgrad_ws_bytes": (_sz, [_i, _i]),
     "dlpd_rotate_trilinear_rgrad": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _ll, _f, _p]),
+    "dlpd_rotate_trilinear_shift": (_i, [_p, _p, _p, _p, _i, _i, _i, _ll, _f, _p]),
+    "dlpd_rotate_trilinear_shift_grad": (_i, [_p, _p, _p, _p, _i, _i, _i, _ll, _f, _i, _p]),
+    "dlpd_rotate_trilinear_pgrad_ws_bytes": (_sz, [_i, _i]),
+    "dlpd_rotate_trilinear_pgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _ll, _f, _p]),
+    "dlpd_local_correlate_shift": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _ll, _ll, _p]),
+    "dlpd_local_correlate_shift_grad": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _ll, _ll, _p]),
     "dlpd_zfft": (_i, [_p, _p, _p, _i, _i, _i, _ll, _i, _f, _p]),
     "dlpd_zfft_into": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _ll, _i, _f, _p]),
     "dlpd_zfft_volumes_occ": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _ll, _i, _p]),

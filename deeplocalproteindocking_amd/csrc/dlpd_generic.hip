@@ -15,6 +15,7 @@
 #include "dlpd_local_grad.h"            // ... and its adjoint (the receptor's and the ligand's gradient)
 #include "dlpd_rotate_grad.h"           // ... and the adjoint of the rotation (the ligand's gradient through the poses)
 #include "dlpd_rotate_rgrad.h"          // ... and the rotation's gradient with respect to its matrix (the poses' own gradient)
+#include "dlpd_rotate_shift.h"          // ... and all of them with a per-pose offset of the sample position (sub-voxel translations)
 
 #define GEN_MAXN 256                      // box sizes up to 128 (tile: n_in x 64 complex <= 128 KB)
 #define GEN_NACC 4                        // partial sums per output of a direct transform (the final adds are written for 4)

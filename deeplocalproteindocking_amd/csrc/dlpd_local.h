@@ -39,10 +39,11 @@ DLPD_HD int local_coarse(int t, int s, int mode) {
 static inline int local_xt(int L) { return L >= 256 ? 1 : (256 / L < L ? 256 / L : L); }   // x-planes per block
 static inline int local_nxb(int L) { const int xt = local_xt(L); return (L + xt - 1) / xt; }
 
-// grid (P * C * nxb, W / NDX), block 256.  part (P, C, nxb, W^3).
+// grid (P * C * nxb, W / NDX), block 256.  part (P, C, nxb, W^3).  off (P, 3) or null: the per-pose offset of the ligand's
+// sample position (dlpd_rotate_shift.h), added to the pivot before the rotated term -- null or zeros: the plain position's bits.
 template <int R, int NDX> __global__ void __launch_bounds__(256)
 k_local_corr(const float* __restrict__ rec, const float* __restrict__ lig, const float* __restrict__ Rm,
-             const int* __restrict__ T, float* __restrict__ part, int C, int L, int XT, int nxb, long long rec_pstride,
+             const float* __restrict__ off, const int* __restrict__ T, float* __restrict__ part, int C, int L, int XT, int nxb, long long rec_pstride,
              long long lig_pstride, float c0, int scale, int mode) {
   constexpr int W = 2 * R + 1, NACC = NDX * W * W, W3 = W * W * W;
   __shared__ float sm[4 * NACC];
@@ -78,6 +79,8 @@ k_local_corr(const float* __restrict__ rec, const float* __restrict__ lig, const
     if (Rm)
       for (int i = 0; i < 9; i++) m[i] = Rm[(size_t)p * 9 + i];
     const float dx = x - c0, dz = z - c0;
+    const float cx = (Rm && off) ? c0 + off[(size_t)p * 3 + 0] : c0, cy = (Rm && off) ? c0 + off[(size_t)p * 3 + 1] : c0,
+                cz = (Rm && off) ? c0 + off[(size_t)p * 3 + 2] : c0;
     float win[W];
 #pragma unroll
     for (int i = 0; i < W; i++) win[i] = 0.f;
@@ -91,9 +94,9 @@ k_local_corr(const float* __restrict__ rec, const float* __restrict__ lig, const
       if (yl < L) {
         if (Rm) {
           const float dy = yl - c0;
-          const float px = c0 + (m[0] * dx + m[3] * dy + m[6] * dz);
-          const float py = c0 + (m[1] * dx + m[4] * dy + m[7] * dz);
-          const float pz = c0 + (m[2] * dx + m[5] * dy + m[8] * dz);
+          const float px = cx + (m[0] * dx + m[3] * dy + m[6] * dz);
+          const float py = cy + (m[1] * dx + m[4] * dy + m[7] * dz);
+          const float pz = cz + (m[2] * dx + m[5] * dy + m[8] * dz);
           v = trilinear_fetch(ligv, L, px, py, pz);
         } else {
           v = ligv[((size_t)x * L + yl) * L + z];
@@ -203,12 +206,41 @@ k_local_filter(const float* __restrict__ corr0, int C0, const float* __restrict_
 }
 
 template <int R, int NDX>
-static int local_corr_launch(const float* rec, const float* lig, const float* Rm, const int* T, float* part, int P, int C, int L,
+static int local_corr_launch(const float* rec, const float* lig, const float* Rm, const float* off, const int* T, float* part, int P, int C, int L,
                              long long rec_pstride, long long lig_pstride, float c0, int scale, int mode, hipStream_t st) {
   const int XT = local_xt(L), nxb = local_nxb(L);
   DLPD_LAUNCH((k_local_corr<R, NDX>), dim3((unsigned)((size_t)P * C * nxb), (unsigned)((2 * R + 1) / NDX)), dim3(256), 0, st, rec,
-              lig, Rm, T, part, C, L, XT, nxb, rec_pstride, lig_pstride, c0, scale, mode);
+              lig, Rm, off, T, part, C, L, XT, nxb, rec_pstride, lig_pstride, c0, scale, mode);
   return DLPD_OK;
+}
+
+extern "C" int dlpd_local_max_poses(int C, int L);
+
+// the body of dlpd_local_correlate and, with `off`, of dlpd_local_correlate_shift (dlpd_rotate_shift.h)
+static int local_correlate_run(const float* rec, const float* lig, const float* R, const float* off, const int* T, float* corr,
+                               void* ws, int P, int C, int L, int r, int scale, int coarse_mode, float center,
+                               long long rec_pstride, long long lig_pstride, void* stream) {
+  if (off && !R) return DLPD_ERR_ARG;              // an offset belongs to a rotated sample
+  if (!rec || !lig || !T || !corr || !ws || P <= 0 || C <= 0 || scale < 1 || rec_pstride < 0 || lig_pstride < 0 ||
+      (coarse_mode != 0 && coarse_mode != 1))
+    return DLPD_ERR_ARG;
+  if (L < 2 || L > DLPD_LOCAL_MAXL || r < 0 || r > DLPD_LOCAL_MAXR) return DLPD_ERR_UNSUPPORTED;
+  // a launch may not exceed 2^32 - 1 threads: 256 per block -> 2^24 - 1 blocks (dlpd_local_max_poses; the caller batches)
+  if (P > dlpd_local_max_poses(C, L)) return DLPD_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)ws;
+  switch (r) {
+    case 0: local_corr_launch<0, 1>(rec, lig, R, off, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
+    case 1: local_corr_launch<1, 3>(rec, lig, R, off, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
+    case 2: local_corr_launch<2, 5>(rec, lig, R, off, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
+    default: local_corr_launch<3, 1>(rec, lig, R, off, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
+  }
+  const int W = 2 * r + 1, W3 = W * W * W;
+  const size_t total = (size_t)P * C * W3;
+  size_t nblk = (total + 255) / 256;
+  if (nblk > 65536) nblk = 65536;
+  DLPD_LAUNCH(k_local_reduce, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)part, corr, (size_t)P * C, local_nxb(L), W3);
+  return dlpd_check_launch();
 }
 
 extern "C" {
@@ -233,26 +265,8 @@ int dlpd_local_max_poses(int C, int L) {
 int dlpd_local_correlate(const float* rec, const float* lig, const float* R, const int* T, float* corr, void* ws, int P, int C,
                          int L, int r, int scale, int coarse_mode, float center, long long rec_pstride, long long lig_pstride,
                          void* stream) {
-  if (!rec || !lig || !T || !corr || !ws || P <= 0 || C <= 0 || scale < 1 || rec_pstride < 0 || lig_pstride < 0 ||
-      (coarse_mode != 0 && coarse_mode != 1))
-    return DLPD_ERR_ARG;
-  if (L < 2 || L > DLPD_LOCAL_MAXL || r < 0 || r > DLPD_LOCAL_MAXR) return DLPD_ERR_UNSUPPORTED;
-  // a launch may not exceed 2^32 - 1 threads: 256 per block -> 2^24 - 1 blocks (dlpd_local_max_poses; the caller batches)
-  if (P > dlpd_local_max_poses(C, L)) return DLPD_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)ws;
-  switch (r) {
-    case 0: local_corr_launch<0, 1>(rec, lig, R, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
-    case 1: local_corr_launch<1, 3>(rec, lig, R, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
-    case 2: local_corr_launch<2, 5>(rec, lig, R, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
-    default: local_corr_launch<3, 1>(rec, lig, R, T, part, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, st); break;
-  }
-  const int W = 2 * r + 1, W3 = W * W * W;
-  const size_t total = (size_t)P * C * W3;
-  size_t nblk = (total + 255) / 256;
-  if (nblk > 65536) nblk = 65536;
-  DLPD_LAUNCH(k_local_reduce, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)part, corr, (size_t)P * C, local_nxb(L), W3);
-  return dlpd_check_launch();
+  return local_correlate_run(rec, lig, R, nullptr, T, corr, ws, P, C, L, r, scale, coarse_mode, center, rec_pstride, lig_pstride,
+                             stream);
 }
 
 // score (P, W^3) [+ best_score (P), best_index (P) int32, either may be null]; T (P, 3) on the FINE grid, scale = fine edge /

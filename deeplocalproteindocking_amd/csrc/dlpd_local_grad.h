@@ -24,9 +24,11 @@
 #define DLPD_LOCAL_GRAD_YC 16        // output rows a thread holds in registers at a time
 
 // grid (NO * C * nxb), NO = P (out_pstride != 0: a gradient per pose) or 1 (one gradient, summed over the P poses); block 256.
+// off (P, 3) or null (ROT only): the per-pose offset of the sample position, as k_local_corr takes it.
 // g (P, C, W^3); sgn = +1: out[q] = sum_d g[d] src[q + tau + d]; sgn = -1: out[q] = sum_d g[d] src[q - tau - d].
 template <int R, bool ROT> __global__ void __launch_bounds__(256)
-k_local_corr_grad(const float* __restrict__ src, const float* __restrict__ Rm, const int* __restrict__ T,
+k_local_corr_grad(const float* __restrict__ src, const float* __restrict__ Rm, const float* __restrict__ off,
+                  const int* __restrict__ T,
                   const float* __restrict__ g, float* __restrict__ out, int P, int C, int L, int XT, int nxb,
                   long long src_pstride, long long out_pstride, float c0, int scale, int mode, int sgn) {
   constexpr int W = 2 * R + 1, W3 = W * W * W, YC = DLPD_LOCAL_GRAD_YC, NJ = YC + 2 * R;
@@ -56,6 +58,8 @@ k_local_corr_grad(const float* __restrict__ src, const float* __restrict__ Rm, c
       float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
       if (ROT)
         for (int i = 0; i < 9; i++) m[i] = Rm[(size_t)p * 9 + i];
+      const float cx = (ROT && off) ? c0 + off[(size_t)p * 3 + 0] : c0, cy = (ROT && off) ? c0 + off[(size_t)p * 3 + 1] : c0,
+                  cz = (ROT && off) ? c0 + off[(size_t)p * 3 + 2] : c0;
       const int ys0 = y0 + ty - R;                 // source row of j = 0; row j feeds the outputs o = j - i, i = e_y + R
       if (ys0 >= L || ys0 + NJ <= 0) continue;     // (block-uniform) no source row of this chunk is in the box
 #pragma unroll 1
@@ -77,9 +81,9 @@ k_local_corr_grad(const float* __restrict__ src, const float* __restrict__ Rm, c
             float v;
             if (ROT) {
               const float dy = ys - c0;
-              const float px = c0 + (m[0] * dx + m[3] * dy + m[6] * dz);
-              const float py = c0 + (m[1] * dx + m[4] * dy + m[7] * dz);
-              const float pz = c0 + (m[2] * dx + m[5] * dy + m[8] * dz);
+              const float px = cx + (m[0] * dx + m[3] * dy + m[6] * dz);
+              const float py = cy + (m[1] * dx + m[4] * dy + m[7] * dz);
+              const float pz = cz + (m[2] * dx + m[5] * dy + m[8] * dz);
               v = trilinear_fetch(srcv, L, px, py, pz);
             } else {
               v = srcv[((size_t)X * L + ys) * L + Z];
@@ -100,29 +104,48 @@ k_local_corr_grad(const float* __restrict__ src, const float* __restrict__ Rm, c
 }
 
 template <int R>
-static void local_grad_launch(const float* src, const float* Rm, const int* T, const float* g, float* out, int P, int C, int L,
+static void local_grad_launch(const float* src, const float* Rm, const float* off, const int* T, const float* g, float* out, int P, int C, int L,
                               long long src_pstride, long long out_pstride, float c0, int scale, int mode, int sgn,
                               hipStream_t st) {
   const int XT = local_xt(L), nxb = local_nxb(L);
   const dim3 grid((unsigned)((size_t)(out_pstride ? P : 1) * C * nxb));
   if (Rm) {
-    DLPD_LAUNCH((k_local_corr_grad<R, true>), grid, dim3(256), 0, st, src, Rm, T, g, out, P, C, L, XT, nxb, src_pstride,
+    DLPD_LAUNCH((k_local_corr_grad<R, true>), grid, dim3(256), 0, st, src, Rm, off, T, g, out, P, C, L, XT, nxb, src_pstride,
                 out_pstride, c0, scale, mode, sgn);
   } else {
-    DLPD_LAUNCH((k_local_corr_grad<R, false>), grid, dim3(256), 0, st, src, Rm, T, g, out, P, C, L, XT, nxb, src_pstride,
+    DLPD_LAUNCH((k_local_corr_grad<R, false>), grid, dim3(256), 0, st, src, Rm, off, T, g, out, P, C, L, XT, nxb, src_pstride,
                 out_pstride, c0, scale, mode, sgn);
   }
 }
 
-static void local_grad_dispatch(int r, const float* src, const float* Rm, const int* T, const float* g, float* out, int P, int C,
+static void local_grad_dispatch(int r, const float* src, const float* Rm, const float* off, const int* T, const float* g, float* out, int P, int C,
                                 int L, long long src_pstride, long long out_pstride, float c0, int scale, int mode, int sgn,
                                 hipStream_t st) {
   switch (r) {
-    case 0: local_grad_launch<0>(src, Rm, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
-    case 1: local_grad_launch<1>(src, Rm, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
-    case 2: local_grad_launch<2>(src, Rm, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
-    default: local_grad_launch<3>(src, Rm, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
+    case 0: local_grad_launch<0>(src, Rm, off, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
+    case 1: local_grad_launch<1>(src, Rm, off, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
+    case 2: local_grad_launch<2>(src, Rm, off, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
+    default: local_grad_launch<3>(src, Rm, off, T, g, out, P, C, L, src_pstride, out_pstride, c0, scale, mode, sgn, st); break;
   }
+}
+
+// the body of dlpd_local_correlate_grad and, with `off`, of dlpd_local_correlate_shift_grad (dlpd_rotate_shift.h)
+static int local_correlate_grad_run(const float* rec, const float* lig, const float* R, const float* off, const int* T,
+                                    const float* gcorr, float* grec, float* glig, int P, int C, int L, int r, int scale,
+                                    int coarse_mode, float center, long long rec_pstride, long long lig_pstride, void* stream) {
+  if (off && !R) return DLPD_ERR_ARG;
+  if (!rec || !lig || !T || !gcorr || (!grec && !glig) || P <= 0 || C <= 0 || scale < 1 || rec_pstride < 0 || lig_pstride < 0 ||
+      (coarse_mode != 0 && coarse_mode != 1))
+    return DLPD_ERR_ARG;
+  if (L < 2 || L > DLPD_LOCAL_MAXL || r < 0 || r > DLPD_LOCAL_MAXR) return DLPD_ERR_UNSUPPORTED;
+  // the ligand's gradient through the rotation is the scatter adjoint of the trilinear gather: not built
+  if (glig && R) return DLPD_ERR_UNSUPPORTED;
+  // a gradient per pose is one block per (pose, channel, slab), as the forward: the same limit of a launch
+  if (((grec && rec_pstride) || (glig && lig_pstride)) && P > dlpd_local_max_poses(C, L)) return DLPD_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (grec) local_grad_dispatch(r, lig, R, off, T, gcorr, grec, P, C, L, lig_pstride, rec_pstride, center, scale, coarse_mode, -1, st);
+  if (glig) local_grad_dispatch(r, rec, nullptr, nullptr, T, gcorr, glig, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, 1, st);
+  return dlpd_check_launch();
 }
 
 extern "C" {
@@ -133,18 +156,8 @@ extern "C" {
 int dlpd_local_correlate_grad(const float* rec, const float* lig, const float* R, const int* T, const float* gcorr, float* grec,
                               float* glig, int P, int C, int L, int r, int scale, int coarse_mode, float center,
                               long long rec_pstride, long long lig_pstride, void* stream) {
-  if (!rec || !lig || !T || !gcorr || (!grec && !glig) || P <= 0 || C <= 0 || scale < 1 || rec_pstride < 0 || lig_pstride < 0 ||
-      (coarse_mode != 0 && coarse_mode != 1))
-    return DLPD_ERR_ARG;
-  if (L < 2 || L > DLPD_LOCAL_MAXL || r < 0 || r > DLPD_LOCAL_MAXR) return DLPD_ERR_UNSUPPORTED;
-  // the ligand's gradient through the rotation is the scatter adjoint of the trilinear gather: not built
-  if (glig && R) return DLPD_ERR_UNSUPPORTED;
-  // a gradient per pose is one block per (pose, channel, slab), as the forward: the same limit of a launch
-  if (((grec && rec_pstride) || (glig && lig_pstride)) && P > dlpd_local_max_poses(C, L)) return DLPD_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (grec) local_grad_dispatch(r, lig, R, T, gcorr, grec, P, C, L, lig_pstride, rec_pstride, center, scale, coarse_mode, -1, st);
-  if (glig) local_grad_dispatch(r, rec, nullptr, T, gcorr, glig, P, C, L, rec_pstride, lig_pstride, center, scale, coarse_mode, 1, st);
-  return dlpd_check_launch();
+  return local_correlate_grad_run(rec, lig, R, nullptr, T, gcorr, grec, glig, P, C, L, r, scale, coarse_mode, center, rec_pstride,
+                                  lig_pstride, stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,8 @@ TorchProteinLibrary's volume ops, backed by libdlpd.so.
     MultiplyVolumes: csrc/dlpd_local_grad.h).  First order; T receives no gradient, and R only where it is asked for:
     ``VolumeRotation(rotation_grad=True)`` and ``local_correlate_rotated(..., rotation_grad=True)`` also return the gradient
     of the rotation matrices (csrc/dlpd_rotate_rgrad.h), what ``Docker.minimize`` descends.
+    The same three calls take ``shift=``: a per-pose translation by a FRACTION of a voxel (csrc/dlpd_rotate_shift.h), which
+    ``rotation_grad=True`` differentiates as well -- the three translational degrees of freedom of ``Docker.minimize(translation=True)``.
     ``conv3d_autograd`` is the plugins' stride-1 convolution with both gradients on the HIP kernels
     (``conv3d_input_grad``, ``conv3d_weight_grad``: csrc/dlpd_conv_grad.h); plain ``conv3d`` stays inference only.
 
@@ -48,14 +50,19 @@ class VolumeRotation(nn.Module):
         self.axis_order = axis_order
         self.transpose = bool(transpose)
 
-    def forward(self, volume, R):
+    def forward(self, volume, R, shift=None):
         """volume (B, C, L, L, L) with R (B, 3, 3), or ONE (C, L, L, L) volume set for all B matrices -> (B, C, L, L, L).
         Differentiable with respect to ``volume`` (first order; csrc/dlpd_rotate_grad.h): when autograd is enabled and the
         volume requires a gradient the call is recorded -- the shared form's gradient is the sum over the B rotations.  ``R``
         receives a gradient only from an operator built with ``rotation_grad=True`` (csrc/dlpd_rotate_rgrad.h: the derivative
         of the trilinear sample, the right-hand one on a cell face; the conventions are folded into the kernel's maps in
         plain torch, so autograd carries it back to ``R``).  In every other case the call is the plain forward (the same
-        bits either way)."""
+        bits either way).
+        ``shift`` (B, 3) float32, voxels of the OUTPUT grid in index order [x][y][z]: the result is the rotated volume
+        displaced by it, out(x) = rotated(x - shift), sampled in one trilinear gather (csrc/dlpd_rotate_shift.h: the kernel's
+        offset off = -M^T shift, folded in plain torch after the conventions -- autograd carries its gradient back to
+        ``shift`` and, through M, to ``R``).  ``shift`` receives a gradient only with ``rotation_grad=True``, as ``R``; zeros
+        give the bits of the call without it."""
         volume, R = _check(volume, "volume", self.lib), _check(R, "R", self.lib)
         if volume.dim() not in (4, 5):
             raise RuntimeError("dlpd: VolumeRotation expects (B, C, L, L, L) or (C, L, L, L), got %s" % (tuple(volume.shape),))
@@ -65,6 +72,13 @@ class VolumeRotation(nn.Module):
         c0 = float(L) / 2.0 if self.center is None else float(self.center)
         if self.scale is not None or self.axis_order != "xyz" or self.transpose:
             R = kernel_matrices(R, rotation_scale(self.scale, L), self.axis_order, self.transpose)
+        if shift is not None:
+            off = _kernel_offset(R, _check(shift, "shift", self.lib))
+            if self.rotation_grad and torch.is_grad_enabled() and (R.requires_grad or off.requires_grad):
+                return _VolumeRotateShift.apply(volume, R, off, c0, self.lib, True)
+            if torch.is_grad_enabled() and volume.requires_grad:
+                return _VolumeRotateShift.apply(volume, R.detach(), off.detach(), c0, self.lib, False)
+            return _volume_rotate_shift_forward(volume, R.detach(), off.detach(), c0, self.lib)
         if self.rotation_grad and torch.is_grad_enabled() and R.requires_grad:
             return _VolumeRotate.apply(volume, R, c0, self.lib, True)
         if torch.is_grad_enabled() and volume.requires_grad:
@@ -111,6 +125,65 @@ class _VolumeRotate(torch.autograd.Function):
             lib_.call("dlpd_rotate_trilinear_rgrad", _ptr(g), _ptr(vol), _ptr(M), _ptr(gM), _ptr(ws), B, C, L, stride, c0,
                       _stream(g.device))
         return gvol, gM, None, None, None
+
+
+def _kernel_offset(M, shift):
+    """The kernels' source-space offset of a displacement by ``shift`` voxels of the output grid: the sample of output voxel x
+    is taken at p(x - shift) = c0 + (x - shift - c0) M, so off = -shift M (``off = -M^T shift``).  Plain torch: differentiable
+    in both."""
+    if shift.dim() != 2 or shift.shape[1] != 3 or shift.shape[0] != M.shape[0]:
+        raise RuntimeError("dlpd: shift must be (%d, 3), one row per matrix, got %s" % (M.shape[0], tuple(shift.shape)))
+    return -torch.matmul(shift.unsqueeze(1), M).squeeze(1).contiguous()
+
+
+def _volume_rotate_shift_forward(volume, M, off, c0, lib):
+    B, C, L = M.shape[0], volume.shape[-4], volume.shape[-1]
+    out = torch.empty(B, C, L, L, L, dtype=torch.float32, device=volume.device)
+    (lib or get_lib()).call("dlpd_rotate_trilinear_shift", _ptr(volume), _ptr(M), _ptr(off), _ptr(out), B, C, L,
+                            C * L ** 3 if volume.dim() == 5 else 0, c0, _stream(volume.device))
+    return out
+
+
+class _VolumeRotateShift(torch.autograd.Function):
+    """VolumeRotation(shift=) under autograd: the forward is dlpd_rotate_trilinear_shift, the backward
+    dlpd_rotate_trilinear_shift_grad for the volume and, for ``pgrad``, dlpd_rotate_trilinear_pgrad for the maps and the offsets."""
+
+    @staticmethod
+    def forward(ctx, volume, M, off, c0, lib, pgrad):
+        M, off = M.contiguous(), off.contiguous()
+        ctx.save_for_backward(M, off, *((volume,) if pgrad else ()))
+        ctx.args = (tuple(volume.shape), c0, lib)
+        return _volume_rotate_shift_forward(volume.detach(), M.detach(), off.detach(), c0, lib)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        M, off = ctx.saved_tensors[0].detach(), ctx.saved_tensors[1].detach()
+        shape, c0, lib = ctx.args
+        lib_ = lib or get_lib()
+        g = _check(gout, "the gradient", lib)
+        B, C, L = M.shape[0], shape[-4], shape[-1]
+        stride = C * L ** 3 if len(shape) == 5 else 0
+        gvol = gM = goff = None
+        if ctx.needs_input_grad[0]:
+            gvol = torch.empty(shape, dtype=torch.float32, device=g.device)
+            lib_.call("dlpd_rotate_trilinear_shift_grad", _ptr(g), _ptr(M), _ptr(off), _ptr(gvol), B, C, L, stride, c0, 0,
+                      _stream(g.device))
+        if len(ctx.saved_tensors) == 3 and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            vol = ctx.saved_tensors[2].detach()
+            gM = torch.empty(B, 3, 3, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1] else None
+            goff = torch.empty(B, 3, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2] else None
+            ws = torch.empty(_pgrad_ws_bytes(lib_, B, L), dtype=torch.uint8, device=g.device)
+            lib_.call("dlpd_rotate_trilinear_pgrad", _ptr(g), _ptr(vol), _ptr(M), _ptr(off), _ptr(gM), _ptr(goff), _ptr(ws), B, C, L,
+                      stride, c0, _stream(g.device))
+        return gvol, gM, goff, None, None, None
+
+
+def _pgrad_ws_bytes(lib_, B, L):
+    n = lib_.call("dlpd_rotate_trilinear_pgrad_ws_bytes", B, L)
+    if n == 0:
+        raise RuntimeError("dlpd: the pose gradient supports boxes 2..128 (box %d)" % L)
+    return n
 
 
 def _rgrad_ws_bytes(lib_, B, L):
@@ -467,7 +540,7 @@ def _pose_volumes(v, P, name, lib):
     return v, v.shape[1] * v.shape[2] ** 3
 
 
-def local_correlate(receptor, ligand, T, R=None, radius=0, scale=1, coarse="floor", center=None, lib=None):
+def local_correlate(receptor, ligand, T, R=None, radius=0, scale=1, coarse="floor", center=None, lib=None, shift=None):
     """corr (P, C, W, W, W), W = 2 radius + 1: corr[p, c, d] = sum_x receptor[c, x + coarse(T_p) + d] * ligand'[c, x], ligand' the
     ligand rotated by R_p (the 3x3 maps ``VolumeRotation`` samples with; None: as it is) -- the slices of
     MultiplyVolumes.multiply (MultiplyVolumes.py:13-47) summed directly.  receptor / ligand: (C, L, L, L) for all poses or
@@ -477,16 +550,23 @@ def local_correlate(receptor, ligand, T, R=None, radius=0, scale=1, coarse="floo
     one of them requires a gradient the call is recorded, and the gradient of a volume shared by all poses is the sum over the
     poses.  ``T`` and ``R`` receive no gradient, and the ligand's gradient THROUGH a rotation (``R`` given) is not this
     function's: that combination raises -- ``local_correlate_rotated`` is the call that has it.  In every other case the call
-    is the plain forward."""
+    is the plain forward.
+    ``shift`` (P, 3) float32, voxels of THIS call's grid (needs ``R``): the rotated ligand is displaced by it, so that the
+    effective translation of pose p is coarse(T_p) + d + shift_p (csrc/dlpd_rotate_shift.h); it receives no gradient here."""
+    off = None
+    if shift is not None:
+        if R is None:
+            raise RuntimeError("dlpd: local_correlate(shift=) needs the rotations R (a fractional translation is a resampling)")
+        off = _kernel_offset(_check(R, "R", lib).detach(), _check(shift, "shift", lib).detach())
     if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in (receptor, ligand)):
         if R is not None and ligand.requires_grad:
             raise RuntimeError("dlpd: local_correlate has no gradient with respect to a ROTATED ligand (R given) -- call "
                                "local_correlate_rotated, which has it, or detach the ligand")
-        return _LocalCorrelate.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib)
-    return _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib)
+        return _LocalCorrelate.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib, off)
+    return _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib, off)
 
 
-def _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib):
+def _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, center, lib, off=None):
     lib_ = lib or get_lib()
     T = T.contiguous()
     if T.dtype != torch.int32 or T.dim() != 2 or T.shape[1] != 3:
@@ -505,8 +585,10 @@ def _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, cent
     per = lib_.call("dlpd_local_ws_bytes", 1, C, L, r)
     if per == 0:
         raise RuntimeError("dlpd: local_correlate supports boxes 2..128 and radius 0..3 (box %d, radius %d)" % (L, r))
+    if off is not None:
+        off = _check(off, "the offset", lib)
     dev = rec.device
-    if T.device != dev or lig.device != dev or (R is not None and R.device != dev):
+    if T.device != dev or lig.device != dev or (R is not None and R.device != dev) or (off is not None and off.device != dev):
         raise RuntimeError("dlpd: local_correlate arguments must be on one device")
     out = torch.empty(P, C, W, W, W, dtype=torch.float32, device=dev)
     chunk = max(1, min(P, LOCAL_WS_BYTES // per, lib_.call("dlpd_local_max_poses", C, L)))      # workspace and launch-grid limits
@@ -515,6 +597,11 @@ def _local_correlate_forward(receptor, ligand, T, R, radius, scale, coarse, cent
     st = _stream(dev)
     for beg in range(0, P, chunk):
         n = min(chunk, P - beg)
+        if off is not None:
+            lib_.call("dlpd_local_correlate_shift", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg, _ptr(R) + 36 * beg,
+                      _ptr(off) + 12 * beg, _ptr(T) + 12 * beg, _ptr(out) + 4 * C * W ** 3 * beg, _ptr(ws), n, C, L, r, int(scale),
+                      COARSE_MODES[coarse], c0, rs, ls, st)
+            continue
         lib_.call("dlpd_local_correlate", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg,
                   (_ptr(R) + 36 * beg) if R is not None else None, _ptr(T) + 12 * beg, _ptr(out) + 4 * C * W ** 3 * beg, _ptr(ws),
                   n, C, L, r, int(scale), COARSE_MODES[coarse], c0, rs, ls, st)
@@ -527,15 +614,15 @@ class _LocalCorrelate(torch.autograd.Function):
     takes every pose in one call (its gradient's grid does not grow with P)."""
 
     @staticmethod
-    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib):
-        ctx.save_for_backward(receptor, ligand, T, R)
+    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib, off=None):
+        ctx.save_for_backward(receptor, ligand, T, R, off)
         ctx.args = (radius, scale, coarse, center, lib)
-        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R, radius, scale, coarse, center, lib)
+        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R, radius, scale, coarse, center, lib, off)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gcorr):
-        receptor, ligand, T, R = ctx.saved_tensors
+        receptor, ligand, T, R, off = ctx.saved_tensors
         r, scale, coarse, center, lib = ctx.args
         lib_ = lib or get_lib()
         T = T.contiguous()
@@ -554,6 +641,12 @@ class _LocalCorrelate(torch.autograd.Function):
         most = lib_.call("dlpd_local_max_poses", C, L)
 
         def run(out_rec, out_lig, beg, n):
+            if off is not None:                       # (with R; only the receptor's gradient is asked for then)
+                lib_.call("dlpd_local_correlate_shift_grad", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg, _ptr(R) + 36 * beg,
+                          _ptr(off) + 12 * beg, _ptr(T) + 12 * beg, _ptr(g) + 4 * C * W ** 3 * beg,
+                          (_ptr(grec) + 4 * rs * beg) if out_rec else None, (_ptr(glig) + 4 * ls * beg) if out_lig else None,
+                          n, C, L, r, int(scale), COARSE_MODES[coarse], c0, rs, ls, st)
+                return
             lib_.call("dlpd_local_correlate_grad", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg,
                       (_ptr(R) + 36 * beg) if R is not None else None, _ptr(T) + 12 * beg, _ptr(g) + 4 * C * W ** 3 * beg,
                       (_ptr(grec) + 4 * rs * beg) if out_rec else None, (_ptr(glig) + 4 * ls * beg) if out_lig else None,
@@ -565,10 +658,11 @@ class _LocalCorrelate(torch.autograd.Function):
                 run(per_rec, per_lig, beg, min(most, P - beg))
         if (want_rec and rs == 0) or (want_lig and ls == 0):
             run(want_rec and rs == 0, want_lig and ls == 0, 0, P)
-        return grec, glig, None, None, None, None, None, None, None
+        return grec, glig, None, None, None, None, None, None, None, None
 
 
-def local_correlate_rotated(receptor, ligand, T, R, radius=0, scale=1, coarse="floor", center=None, lib=None, rotation_grad=False):
+def local_correlate_rotated(receptor, ligand, T, R, radius=0, scale=1, coarse="floor", center=None, lib=None, rotation_grad=False,
+                            shift=None):
     """``local_correlate(receptor, ligand, T, R=R, ...)`` -- the same call, the same bits, no rotated volume in memory --
     differentiable in BOTH volumes: what trains a model on the poses of a search's top list (rotations of one ligand).
     The receptor's gradient is the correlation's adjoint kernel with R (it recomputes the sample).  The ligand's goes in two
@@ -577,9 +671,22 @@ def local_correlate_rotated(receptor, ligand, T, R, radius=0, scale=1, coarse="f
     its rotations -- summed over the poses, in pose order, for a ligand shared by all of them.  First order; ``T`` receives
     no gradient, and ``R`` only with ``rotation_grad=True``: the same workspace contracted with the derivative of the trilinear
     sample (csrc/dlpd_rotate_rgrad.h) gives the nine numbers of every pose, each from one kernel call -- chunking does not
-    change their bits."""
+    change their bits.
+    ``shift`` (P, 3) float32, voxels of this call's grid: the rotated ligand displaced by a fraction of a voxel, as
+    ``local_correlate`` takes it -- the effective translation of pose p is coarse(T_p) + d + shift_p.  Every gradient above goes
+    through the offset kernels (csrc/dlpd_rotate_shift.h), and ``rotation_grad=True`` also differentiates ``shift`` (three more
+    numbers per pose from the same kernel call; through off = -M^T shift they reach R too)."""
     if R is None:
         raise RuntimeError("dlpd: local_correlate_rotated needs the rotations R (without them: local_correlate)")
+    if shift is not None:
+        pose = rotation_grad and torch.is_grad_enabled()
+        off = _kernel_offset(_check(R, "R", lib), _check(shift, "shift", lib))
+        if pose and (R.requires_grad or off.requires_grad):
+            return _LocalCorrelateRotated.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib, True, off)
+        if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in (receptor, ligand)):
+            return _LocalCorrelateRotated.apply(receptor, ligand, T, R.detach(), int(radius), int(scale), coarse, center, lib, False,
+                                                off.detach())
+        return _local_correlate_forward(receptor, ligand, T, R.detach(), radius, scale, coarse, center, lib, off.detach())
     if rotation_grad and torch.is_grad_enabled() and R.requires_grad:
         return _LocalCorrelateRotated.apply(receptor, ligand, T, R, int(radius), int(scale), coarse, center, lib, True)
     if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in (receptor, ligand)):
@@ -593,15 +700,16 @@ class _LocalCorrelateRotated(torch.autograd.Function):
     (``accumulate``): the chunked result has the bits of the unsplit one."""
 
     @staticmethod
-    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib, rgrad=False):
-        ctx.save_for_backward(receptor, ligand, T, R)
+    def forward(ctx, receptor, ligand, T, R, radius, scale, coarse, center, lib, rgrad=False, off=None):
+        ctx.save_for_backward(receptor, ligand, T, R, off)
         ctx.args = (radius, scale, coarse, center, lib, rgrad)
-        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R.detach(), radius, scale, coarse, center, lib)
+        return _local_correlate_forward(receptor.detach(), ligand.detach(), T, R.detach(), radius, scale, coarse, center, lib,
+                                        None if off is None else off.detach())
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gcorr):
-        receptor, ligand, T, R = ctx.saved_tensors
+        receptor, ligand, T, R, off = ctx.saved_tensors
         r, scale, coarse, center, lib, rgrad = ctx.args
         lib_ = lib or get_lib()
         T = T.contiguous()
@@ -613,6 +721,10 @@ class _LocalCorrelateRotated(torch.autograd.Function):
         C, L, W = rec.shape[-4], rec.shape[-1], 2 * r + 1
         vol = C * L ** 3
         want_rec, want_lig, want_R = ctx.needs_input_grad[0], ctx.needs_input_grad[1], rgrad and ctx.needs_input_grad[3]
+        want_off = off is not None and rgrad and ctx.needs_input_grad[10]
+        goff = torch.empty(P, 3, dtype=torch.float32, device=rec.device) if want_off else None
+        if off is not None:
+            off = _check(off.detach(), "the offset", lib)
         gR = torch.empty(P, 3, 3, dtype=torch.float32, device=rec.device) if want_R else None
         grec = torch.empty_like(rec) if want_rec else None
         glig = torch.empty_like(lig) if want_lig else None
@@ -621,6 +733,11 @@ class _LocalCorrelateRotated(torch.autograd.Function):
         most = lib_.call("dlpd_local_max_poses", C, L)
 
         def run(Rp, out_rec, out_lig, lig_stride, beg, n):
+            if off is not None and Rp is not None:
+                lib_.call("dlpd_local_correlate_shift_grad", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg, Rp,
+                          _ptr(off) + 12 * beg, _ptr(T) + 12 * beg, _ptr(g) + 4 * C * W ** 3 * beg, out_rec, out_lig, n, C, L, r,
+                          int(scale), COARSE_MODES[coarse], c0, rs, lig_stride, st)
+                return
             lib_.call("dlpd_local_correlate_grad", _ptr(rec) + 4 * rs * beg, _ptr(lig) + 4 * ls * beg, Rp, _ptr(T) + 12 * beg,
                       _ptr(g) + 4 * C * W ** 3 * beg, out_rec, out_lig, n, C, L, r, int(scale), COARSE_MODES[coarse], c0, rs,
                       lig_stride, st)
@@ -628,21 +745,32 @@ class _LocalCorrelateRotated(torch.autograd.Function):
             step = most if rs != 0 else P             # a gradient per pose: one launch's poses; a shared receptor: all in one call
             for beg in range(0, P, step):
                 run(_ptr(R) + 36 * beg, _ptr(grec) + 4 * rs * beg, None, ls, beg, min(step, P - beg))
-        if want_lig or want_R:
+        if want_lig or want_R or want_off:
             chunk = max(1, min(P, LOCAL_WS_BYTES // (4 * vol), most))
             ws = torch.empty(chunk * vol, dtype=torch.float32, device=rec.device)
-            if want_R:
+            if off is not None and (want_R or want_off):
+                ws_r = torch.empty(_pgrad_ws_bytes(lib_, chunk, L), dtype=torch.uint8, device=rec.device)
+            elif want_R:
                 ws_r = torch.empty(_rgrad_ws_bytes(lib_, chunk, L), dtype=torch.uint8, device=rec.device)
             for beg in range(0, P, chunk):
                 n = min(chunk, P - beg)
                 run(None, None, _ptr(ws), vol, beg, n)             # the gradient of each pose's rotated ligand (no ligand is read)
+                if off is not None:                                # the same two steps through the offset kernels
+                    if want_lig:
+                        lib_.call("dlpd_rotate_trilinear_shift_grad", _ptr(ws), _ptr(R) + 36 * beg, _ptr(off) + 12 * beg,
+                                  _ptr(glig) + 4 * ls * beg, n, C, L, ls, c0, 1 if (ls == 0 and beg > 0) else 0, st)
+                    if want_R or want_off:                         # 12 numbers per pose: the nine of R, the three of the offset
+                        lib_.call("dlpd_rotate_trilinear_pgrad", _ptr(ws), _ptr(lig) + 4 * ls * beg, _ptr(R) + 36 * beg,
+                                  _ptr(off) + 12 * beg, (_ptr(gR) + 36 * beg) if want_R else None,
+                                  (_ptr(goff) + 12 * beg) if want_off else None, _ptr(ws_r), n, C, L, ls, c0, st)
+                    continue
                 if want_lig:
                     lib_.call("dlpd_rotate_trilinear_grad", _ptr(ws), _ptr(R) + 36 * beg, _ptr(glig) + 4 * ls * beg, n, C, L, ls,
                               c0, 1 if (ls == 0 and beg > 0) else 0, st)
                 if want_R:                                         # ... contracted with the sample's derivative: 9 numbers per pose
                     lib_.call("dlpd_rotate_trilinear_rgrad", _ptr(ws), _ptr(lig) + 4 * ls * beg, _ptr(R) + 36 * beg,
                               _ptr(gR) + 36 * beg, _ptr(ws_r), n, C, L, ls, c0, st)
-        return grec, glig, None, gR, None, None, None, None, None, None
+        return grec, glig, None, gR, None, None, None, None, None, None, goff
 
 
 def local_coarse_radius(radius, scale):

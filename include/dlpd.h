@@ -88,6 +88,27 @@ int dlpd_rotate_trilinear_grad(const float* gout, const float* R, float* gvol, i
 size_t dlpd_rotate_trilinear_rgrad_ws_bytes(int B, int L);
 int dlpd_rotate_trilinear_rgrad(const float* gout, const float* vol, const float* R, float* gR, void* ws, int B, int C, int L,
                                 long long vol_bstride, float center, void* stream);
+/* SUB-VOXEL TRANSLATIONS: the same rotation with a per-pose offset of the sample position,
+ *   p_a(i) = (center + off[b][a]) + sum_j R[b][3j + a] (i_j - center),   off (B,3) float32 in voxels of the source volume, laid
+ *   out like a row of R's columns; null: zeros.  center + off is added first, the rotated term then: with off = 0 (or null) every
+ *   entry returns the bits of the plain entry.  A volume rotated and then displaced by s voxels is off = -R^T s.
+ * dlpd_rotate_trilinear_shift: the forward (vol, R, out, vol_bstride as dlpd_rotate_trilinear; every element written).
+ * dlpd_rotate_trilinear_shift_grad: its adjoint with respect to the volume -- dlpd_rotate_trilinear_grad with the offset (the
+ *   candidates of a source voxel q are centred on center + A^-1 (q - center - off)); the same guarantees: no atomics, every
+ *   element written, accumulate, exact for any invertible map.
+ * dlpd_rotate_trilinear_pgrad: the pose gradient -- gR (B,9) as dlpd_rotate_trilinear_rgrad, and
+ *   goff[b][a] = sum_c sum_i gout[b,c](i) * d_a vol[b,c]( p_b(i) )   (B,3); either may be null (not wanted), not both.
+ *   The same order of additions as the nine-number entry (its gR at off = 0 has that entry's bits); twelve float64 partials per
+ *   block in ws (dlpd_rotate_trilinear_pgrad_ws_bytes(B, L) bytes; 0 for an unsupported shape), added in block order; a pose's
+ *   twelve numbers do not depend on the other poses of its call.
+ * Null pointers, B or C <= 0 or a negative stride: DLPD_ERR_ARG; L < 2 or L > 128: DLPD_ERR_UNSUPPORTED. */
+int dlpd_rotate_trilinear_shift(const float* vol, const float* R, const float* off, float* out, int B, int C, int L,
+                                long long vol_bstride, float center, void* stream);
+int dlpd_rotate_trilinear_shift_grad(const float* gout, const float* R, const float* off, float* gvol, int B, int C, int L,
+                                     long long gvol_bstride, float center, int accumulate, void* stream);
+size_t dlpd_rotate_trilinear_pgrad_ws_bytes(int B, int L);
+int dlpd_rotate_trilinear_pgrad(const float* gout, const float* vol, const float* R, const float* off, float* gR, float* goff,
+                                void* ws, int B, int C, int L, long long vol_bstride, float center, void* stream);
 
 /* Stage K1 of TPL VolumeConvolution (src/Models/DockingModels.py:71, src/Docker/Docker.py:225),
  * optionally fused with the rotation of Docker.py:218: z-axis R2C of (rotated) volumes.
@@ -272,6 +293,16 @@ int dlpd_local_correlate(const float* rec, const float* lig, const float* R, con
 int dlpd_local_correlate_grad(const float* rec, const float* lig, const float* R, const int* T, const float* gcorr, float* grec,
                               float* glig, int P, int C, int L, int r, int scale, int coarse_mode, float center,
                               long long rec_pstride, long long lig_pstride, void* stream);
+/* Both with the ligand sampled at a per-pose offset (sub-voxel translations; off (P,3) as dlpd_rotate_trilinear_shift takes it):
+ *   corr[p,c,d] = sum_x rec[c, x + tau] lig_c( (center + off_p) + R_p^T (x - center) ).
+ * The arguments, workspace, limits and error codes of the plain entries, `off` after R; off null: the plain entry's bits; off
+ * without R: DLPD_ERR_ARG; glig with R stays DLPD_ERR_UNSUPPORTED (dlpd_rotate_trilinear_shift_grad carries that gradient). */
+int dlpd_local_correlate_shift(const float* rec, const float* lig, const float* R, const float* off, const int* T, float* corr,
+                               void* ws, int P, int C, int L, int r, int scale, int coarse_mode, float center,
+                               long long rec_pstride, long long lig_pstride, void* stream);
+int dlpd_local_correlate_shift_grad(const float* rec, const float* lig, const float* R, const float* off, const int* T,
+                                    const float* gcorr, float* grec, float* glig, int P, int C, int L, int r, int scale,
+                                    int coarse_mode, float center, long long rec_pstride, long long lig_pstride, void* stream);
 /* The filter of those poses (DockingModels.py:118-119; with clip / clash the search's DockingModels.py:74-83, Docker.py:226,232):
  * feat[d] = [clamp(corr0[:, d]), clamp(corr1[:, coarse(T_p + d) - coarse(T_p)])], score (P, W^3) = MLP(feat) * (clash < thr).
  * corr0 (P, C0, W^3) from dlpd_local_correlate(scale 1, r); corr1 (P, C1, Wc^3) from dlpd_local_correlate(scale, rc)

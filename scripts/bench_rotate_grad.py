@@ -13,7 +13,10 @@ LocalDockingModel.forward_poses step (forward + backward).  Prints one JSON line
                                                                              #   matrices (csrc/dlpd_rotate_rgrad.h): the backward
                                                                              #   of local_correlate_rotated with and without
                                                                              #   rotation_grad, the new kernel beside the adjoint on
-                                                                             #   one workspace, Docker.minimize beside Docker.refine
+                                                                             #   one workspace, the twelve-number kernel
+                                                                             #   (csrc/dlpd_rotate_shift.h: + the offset's gradient)
+                                                                             #   beside it, Docker.minimize with and without
+                                                                             #   translation=True beside Docker.refine
 
 The adjoint's floor is memory traffic: it reads B C L^3 4 bytes (the gradient of every rotated copy) and writes C L^3 4.
 Needs a GPU: no CPU fallback."""
@@ -143,6 +146,23 @@ def pose_grad_rows(lib, dev, P, repeats, variants=()):
         row["rgrad_floor_bytes"] = (P + 1) * C * L ** 3 * 4
         row["rgrad_achieved_TB_per_s"] = row["rgrad_floor_bytes"] / (row["k_rotate_rgrad_ms"]["median"] * 1e-3) / 1e12
         print(json.dumps(row), flush=True)
+        # the twelve-number kernel (gR and goff) beside the nine-number one, without and with a non-zero offset: each twice,
+        # alternating
+        goff = torch.empty(P, 3, device=dev)
+        part12 = torch.empty(lib.call("dlpd_rotate_trilinear_pgrad_ws_bytes", P, L), dtype=torch.uint8, device=dev)
+        offs = {"zero_offset": torch.zeros(P, 3, device=dev),
+                "offset": torch.from_numpy(np.random.RandomState(11).uniform(-0.5, 0.5, size=(P, 3)).astype(np.float32)).to(dev)}
+        row = {"part": "nine numbers (dlpd_rotate_trilinear_rgrad) beside twelve (dlpd_rotate_trilinear_pgrad) %d @ %d^3, %d poses "
+                       "(device events, kernel + reduce, alternating)" % (C, L, P)}
+        for rnd in range(2):
+            row["rgrad_ms_round%d" % rnd] = _timed(lambda: lib.call(
+                "dlpd_rotate_trilinear_rgrad", ws.data_ptr(), lig.data_ptr(), R.data_ptr(), gR.data_ptr(), part.data_ptr(), P, C, L, 0, c0,
+                st), repeats)["median"]
+            for name, off in offs.items():
+                row["pgrad_%s_ms_round%d" % (name, rnd)] = _timed(lambda: lib.call(
+                    "dlpd_rotate_trilinear_pgrad", ws.data_ptr(), lig.data_ptr(), R.data_ptr(), off.data_ptr(), gR.data_ptr(), goff.data_ptr(),
+                    part12.data_ptr(), P, C, L, 0, c0, st), repeats)["median"]
+        print(json.dumps(row), flush=True)
         if variants:                                          # A/B builds of the kernel: every library twice, alternating
             row = {"part": "k_rotate_rgrad variants %d @ %d^3, %d poses (device events, alternating)" % (C, L, P)}
             for rnd in range(2):
@@ -177,8 +197,9 @@ def minimize_row(dev, npose, steps=20, rounds=3):
     with torch.no_grad():
         top = list(dk.dock_volumes(rec, lig, recf, ligf, write=False))
     dk.release_engine()
-    calls = {"refine": lambda: dk.refine(rec, lig, recf, ligf, poses=top), "minimize": lambda: dk.minimize(rec, lig, recf, ligf, poses=top, steps=steps)}
-    ms, lists = {"refine": [], "minimize": []}, {}
+    calls = {"refine": lambda: dk.refine(rec, lig, recf, ligf, poses=top), "minimize": lambda: dk.minimize(rec, lig, recf, ligf, poses=top, steps=steps),
+             "minimize_translation": lambda: dk.minimize(rec, lig, recf, ligf, poses=top, steps=steps, translation=True)}
+    ms, lists = {name: [] for name in calls}, {}
     for rnd in range(rounds + 1):
         for name, fn in calls.items():
             torch.cuda.synchronize()
@@ -187,7 +208,7 @@ def minimize_row(dev, npose, steps=20, rounds=3):
             torch.cuda.synchronize()
             if rnd > 0:
                 ms[name].append(1e3 * (time.perf_counter() - t0) / len(top))
-    row = {"part": "Docker.minimize(steps=%d) beside Docker.refine(5 degrees, 1), %d poses of a 256-rotation search, real_protein "
+    row = {"part": "Docker.minimize(steps=%d), without and with translation=True, beside Docker.refine(5 degrees, 1), %d poses of a 256-rotation search, real_protein "
                    "volumes [16 @ 80^3, 32 @ 40^3] (wall time)" % (steps, len(top)), "search_scores": [top[0][4], float(np.mean([t[4] for t in top]))]}
     for name in calls:
         sc = [e[2] for e in lists[name]]
@@ -196,7 +217,28 @@ def minimize_row(dev, npose, steps=20, rounds=3):
                      "improved": int(sum(e[2] < top[e[3]][4] for e in lists[name]))}
     by = {e[3]: e[2] for e in lists["refine"]}
     row["minimize_below_refine"] = int(sum(e[2] < by[e[3]] for e in lists["minimize"]))
+    row["minimize_translation_below_refine"] = int(sum(e[2] < by[e[3]] for e in lists["minimize_translation"]))
+    by = {e[3]: e[2] for e in lists["minimize"]}
+    row["minimize_translation_below_minimize"] = int(sum(e[2] < by[e[3]] for e in lists["minimize_translation"]))
     print(json.dumps(row), flush=True)
+
+
+def _variant_lib(path):
+    """An A/B build for --pose-grad, which may be the library of ANOTHER commit (the parent's build, to hold a kernel's time to
+    what it was): bound to the entry points it has, not to the whole of today's header."""
+    import ctypes
+    from deeplocalproteindocking_amd._lib import SIGNATURES, DlpdLib
+
+    class Partial(DlpdLib):
+        def __init__(self, path):
+            self.path = path
+            self._dll = ctypes.CDLL(path)
+            for name, (res, args) in SIGNATURES.items():
+                fn = getattr(self._dll, name, None)
+                if fn is not None:
+                    fn.restype, fn.argtypes = res, args
+                    setattr(self, "_" + name, fn)
+    return Partial(path)
 
 
 def _stats(directory):
@@ -236,9 +278,8 @@ def main():
         torch.cuda.synchronize()
         return
     if args.pose_grad:
-        from deeplocalproteindocking_amd._lib import DlpdLib
         pose_grad_rows(lib, dev, P, args.repeats,
-                       [(nv.split("=")[0], DlpdLib(nv.split("=")[1])) for nv in args.variants.split(",") if nv])
+                       [(nv.split("=")[0], _variant_lib(nv.split("=")[1])) for nv in args.variants.split(",") if nv])
         torch.cuda.empty_cache()
         if args.minimize_poses > 0:
             minimize_row(dev, args.minimize_poses)

@@ -8,6 +8,8 @@ without the benchmark table: representation -> exhaustive rotation x translation
                                            # RADIUS voxels (default 1) -> <out>.refined.dat beside the .dat
         [--minimize STEPS]                 # SE3: descend the score of every pose of the top list in its rotation, at most STEPS
                                            # trials per pose (Docker.minimize) -> <out>.minimized.dat beside the .dat
+        [--minimize-translation]           # with --minimize: a rigid-body descent, the translation moves by fractions of a voxel
+                                           # too (Docker.minimize(translation=True)); the .dat carries T + s times the resolution
 
 Multi-GPU: launch with torch.distributed.run; rotations are sharded over the ranks, rank 0 writes."""
 import argparse
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("-load_epoch", default=0, type=int)
     ap.add_argument("--refine", default=None, metavar="ANGLE[:STEPS[:RADIUS]]")
     ap.add_argument("--minimize", default=None, type=int, metavar="STEPS")
+    ap.add_argument("--minimize-translation", action="store_true")
     args = ap.parse_args()
     entry.build()
     from deeplocalproteindocking_amd.Docker import Docker
@@ -66,6 +69,8 @@ def main():
             ap.error("--refine needs -group SE3 (the ligand's volumes are rotated, not re-represented)")
         part = args.refine.split(":")
         refine = (float(part[0]), int(part[1]) if len(part) > 1 else 1, int(part[2]) if len(part) > 2 else 1)
+    if args.minimize_translation and args.minimize is None:
+        ap.error("--minimize-translation needs --minimize STEPS")
     if args.minimize is not None and args.group != "SE3":
         ap.error("--minimize needs -group SE3 (the ligand's volumes are rotated, not re-represented)")
     with torch.no_grad():
@@ -84,7 +89,7 @@ def main():
             docker.cleanup()
             print("wrote", name, "(%d poses, best score %f)" % (len(docker.refined_list), docker.refined_list[0][2]))
     if args.minimize is not None:
-        docker.minimize_prepared(prepared, steps=args.minimize)
+        docker.minimize_prepared(prepared, steps=args.minimize, translation=args.minimize_translation)
         if rank == 0:           # every rank minimised the same gathered list
             name = (args.out[:-4] if args.out.endswith(".dat") else args.out) + ".minimized.dat"
             docker.new_log(name, rewrite=True)
