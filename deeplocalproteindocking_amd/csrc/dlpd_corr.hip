@@ -275,6 +275,15 @@ k_rotate_zfft(const float* __restrict__ vol, const float* __restrict__ R, cplx* 
 // and CHUNK-MAJOR [chunk][x][y][z][CC] (vstride = CC / 4, cstride = L^3 CC / 4; dlpd_make_channel_chunks), where a
 // block's CC channels of neighbouring z fill whole 128-byte lines instead of a CC-channel slice of each voxel's record.
 // Only addresses differ: same samples, same spectra.
+// ZP (chunk-major source at N = 128, launch_k1_cl; dlpd_k1.h ZPAIR, -DDLPD_K1_ZPAIR=0 builds without): four lanes per
+// (row pair, z) task, lane = 4 voxel + 2 zc + q, lane zc producing row 2m + zc -- so a lane stores its 4-byte HALF of the
+// four pencil elements (real part: zc = 0) with ds_write_b32 where the two-lane gather stores whole elements with
+// ds_write_b64.  Bank model of that store: ds_write_b32 is served in two groups of 32 lanes over 32 four-byte banks; a group
+// is 8 consecutive z x 2 zc x 2 q of one row pair m, at dword 2 (row(q, m) RS + SKEW q + z) + zc.  The rows of the two
+// quads lie 32 RS elements apart (a multiple of 32 banks), so the bank is 2 z + zc + 2 SKEW q + const: 16 consecutive banks
+// per quad, and SKEW = 8 puts the second quad on the other 16 -- conflict-free with the SKEW the 8-byte stores already
+// needed (there: groups of 16 lanes, 8 z x 2 q, 16 + 16 banks).  DLPD_K1_ZPAIR_DEPTH tasks are issued before the first is
+// consumed: 16 loads in flight per lane as in the two-lane gather, 124 registers, no scratch.
 // ------------------------------------------------------------------------------------------
 // OCC (round 6, its own instantiation: the dense callers run the code they always ran): `occ` (nb, ceil(L/4)^3) bytes,
 // [x cell][y cell][z cell] per rotation, 0 = every sample of that 4 x 4 x 4 cell of the ROTATED volume is zero
@@ -282,7 +291,7 @@ k_rotate_zfft(const float* __restrict__ vol, const float* __restrict__ R, cplx* 
 // zero away from the protein, so most pencils of a rotated volume are empty: a task in an empty cell skips its sixteen
 // loads (the sample is the +0.0 the sum of zero products is), a block whose cells are all empty skips the transform too
 // and writes its zeros.  Exact; same spectra as without the map.
-template <int N, bool OCC> __global__ void __launch_bounds__(K1ClCfg<N>::NP * FftPlan<N>::T)
+template <int N, bool OCC, bool ZP = false> __global__ void __launch_bounds__(K1ClCfg<N>::NP * FftPlan<N>::T)
 k_rotate_zfft_cl(const float4* __restrict__ cl, const float* __restrict__ R, cplx* __restrict__ A,
                  int C, int nchunk, int vstride, int cstride, int nb, float c0, int CT_out, int c_base, int ext,
                  const unsigned char* __restrict__ occ, int skip_empty) {
@@ -335,20 +344,50 @@ k_rotate_zfft_cl(const float4* __restrict__ cl, const float* __restrict__ R, cpl
   init_twiddles<N>(tw, tid, NT);
   {
     const K1ClRot rot = k1cl_load_rotation(R + (size_t)b * 9);
-    for (int task = tid; task < NPR * L * LPV; task += NT) {
-      const int q = task % LPV, z = (task / LPV) % L, m = (task / LPV) / L;
-      const float4* src = cl + (size_t)chunk * cstride + q;
-      float4 acc[2];
-      if (OCC && !occ_s[((2 * m) >> 2) * NC + (z >> 2)])       // rows 2m, 2m + 1 lie in one cell
-        acc[0] = acc[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      else
-        k1cl_sample_rows(src, vstride, L, ext, c0, rot, x, yg * YG + 2 * m, z, acc);
-      // rows 2m (real part) and 2m+1 (imaginary part) of the four channels' pencils
-      cplx* P = S + ((4 * q) * NPR + m) * RS + SKEW * q + z;
-      P[0] = c_make(acc[0].x, acc[1].x);
-      P[NPR * RS] = c_make(acc[0].y, acc[1].y);
-      P[2 * NPR * RS] = c_make(acc[0].z, acc[1].z);
-      P[3 * NPR * RS] = c_make(acc[0].w, acc[1].w);
+    if constexpr (ZP) {
+      static_assert(LPV == 2 && (NPR * L * 4) % NT == 0 && L % 16 == 0, "whole waves of four-lane tasks, one row pair per wave");
+      constexpr int DEPTH = DLPD_K1_ZPAIR_DEPTH;
+      static_assert((NPR * L * 4) % (DEPTH * NT) == 0, "every lane has DEPTH tasks per round");
+      for (int task0 = tid; task0 < NPR * L * 4; task0 += DEPTH * NT) {
+        K1ClZpairTask tk[DEPTH];
+#pragma unroll
+        for (int i = 0; i < DEPTH; i++) {
+          const int task = task0 + i * NT;
+          const int q = task & 1, zc = (task >> 1) & 1, z = (task >> 2) % L, m = (task >> 2) / L;
+          const bool gather = !OCC || occ_s[((2 * m) >> 2) * NC + (z >> 2)];   // the same for the four lanes of a task
+          // (voxel stride LPV = vstride of the chunk-major copy, as a constant: the offsets are shifts, not 64-bit multiplies)
+          k1cl_zpair_issue(tk[i], cl + (size_t)chunk * cstride + q, LPV, L, ext, c0, rot, x, yg * YG + 2 * m, z, zc, gather);
+        }
+        DLPD_SCHED_FENCE();              // all 8 DEPTH loads are issued before the first is waited for (the scheduler sank them otherwise)
+#pragma unroll
+        for (int i = 0; i < DEPTH; i++) {
+          const int task = task0 + i * NT;
+          const int q = task & 1, zc = (task >> 1) & 1, z = (task >> 2) % L, m = (task >> 2) / L;
+          const float4 acc = k1cl_zpair_finish(tk[i]);
+          // row 2m + zc: the real (zc = 0) or imaginary half of the four channels' pencil elements
+          float* P = reinterpret_cast<float*>(S + ((4 * q) * NPR + m) * RS + SKEW * q + z) + zc;
+          P[0] = acc.x;
+          P[2 * NPR * RS] = acc.y;
+          P[4 * NPR * RS] = acc.z;
+          P[6 * NPR * RS] = acc.w;
+        }
+      }
+    } else {
+      for (int task = tid; task < NPR * L * LPV; task += NT) {
+        const int q = task % LPV, z = (task / LPV) % L, m = (task / LPV) / L;
+        const float4* src = cl + (size_t)chunk * cstride + q;
+        float4 acc[2];
+        if (OCC && !occ_s[((2 * m) >> 2) * NC + (z >> 2)])       // rows 2m, 2m + 1 lie in one cell
+          acc[0] = acc[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        else
+          k1cl_sample_rows(src, vstride, L, ext, c0, rot, x, yg * YG + 2 * m, z, acc);
+        // rows 2m (real part) and 2m+1 (imaginary part) of the four channels' pencils
+        cplx* P = S + ((4 * q) * NPR + m) * RS + SKEW * q + z;
+        P[0] = c_make(acc[0].x, acc[1].x);
+        P[NPR * RS] = c_make(acc[0].y, acc[1].y);
+        P[2 * NPR * RS] = c_make(acc[0].z, acc[1].z);
+        P[3 * NPR * RS] = c_make(acc[0].w, acc[1].w);
+      }
     }
   }
   __syncthreads();
@@ -428,6 +467,20 @@ template <int N> static int launch_k1_cl(const float4* cl, const float* R, cplx*
   const int gper = (nb * L + 7) / 8;
   dim3 grid((unsigned)(8 * gper * per)), block(K1ClCfg<N>::NP * FftPlan<N>::T);
   const int e = (ext > 0 && ext < L) ? ext : L;
+  if constexpr (K1ClZpair<N>::ON) {                              // chunk-major at N = 128: four lanes per (row pair, z), dlpd_k1.h
+    if (chunk_major) {
+      int rc = occ ? dlpd_set_max_dyn_shared((const void*)k_rotate_zfft_cl<N, true, true>, shmem)
+                   : dlpd_set_max_dyn_shared((const void*)k_rotate_zfft_cl<N, false, true>, shmem);
+      if (rc) return rc;
+      if (occ)
+        DLPD_LAUNCH((k_rotate_zfft_cl<N, true, true>), grid, block, shmem, st, cl, R, A, C, nchunk, vstride, cstride, nb, c0, CT_out,
+                    c_base, e, occ, skip_empty);
+      else
+        DLPD_LAUNCH((k_rotate_zfft_cl<N, false, true>), grid, block, shmem, st, cl, R, A, C, nchunk, vstride, cstride, nb, c0, CT_out,
+                    c_base, e, occ, 0);
+      return dlpd_check_launch();
+    }
+  }
   if (occ) {
     int rc = dlpd_set_max_dyn_shared((const void*)k_rotate_zfft_cl<N, true>, shmem);
     if (rc) return rc;

@@ -104,6 +104,17 @@ __device__ __forceinline__ dlpd_f2v dlpd_f2_splat(float a) { dlpd_f2v r = {a, a}
 __device__ __forceinline__ float dlpd_f2_get(dlpd_f2v v, int i) { return i ? v.y : v.x; }
 __device__ __forceinline__ dlpd_f2v dlpd_pk_fma(dlpd_f2v a, dlpd_f2v b, dlpd_f2v c) { return __builtin_elementwise_fma(a, b, c); }
 
+// the value lane ^ 2 holds (the other lane pair of an aligned group of four lanes): one DPP move per register
+// (quad_perm:[2,3,0,1]), no LDS traffic and no wait.  Both lanes must be active.  (The emulator build has no DPP: its twin
+// next to the caller, dlpd_k1.h, is a wave shuffle.)
+__device__ __forceinline__ float dlpd_quad_swap2(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float4 dlpd_quad_swap2(float4 v) {
+  return make_float4(dlpd_quad_swap2(v.x), dlpd_quad_swap2(v.y), dlpd_quad_swap2(v.z), dlpd_quad_swap2(v.w));
+}
+#define DLPD_HAS_QUAD_SWAP2 1
+
 // table[bin] += 1 for every lane of the wave with `hit`, WITHOUT an LDS atomic: the lanes that name the same bin are found
 // with ballots (scalar work only: `v_readlane` of the group's bin, one compare, one population count per DIFFERENT bin in
 // the wave), the first lane of every group keeps the group's size, and then all of those lanes -- their bins are different --
