@@ -11,6 +11,9 @@ What differs is where the arithmetic runs: ``forward`` is one VolumeConvolution(
 instead of interpolate / cat / three transposes / two GEMMs (DockingModels.py:74-83).  ``filter`` may
 be ANY module mapping (voxels, channels) -> (voxels, 1) (DockingModels.py:82): a filter that is not
 that MLP is called on the reference's own channels-last layout.
+``GlobalDockingModel(differentiable=True)`` is the model that is trained: under autograd its correlations are the
+differentiable ``VolumeConvolution`` (the adjoint FFT kernels of csrc/dlpd_corr_grad.h) and its filter is called, so a loss
+over the whole (2L)^3 translation grid reaches the filter's and the representation's parameters.
 """
 import os
 
@@ -85,9 +88,16 @@ class GlobalDockingModel(nn.Module):
     FILES = ("%s_repr_epoch%d.th", "%s_filter_epoch%d.th")
 
     def __init__(self, representation, filter, threshold_clash=300, normalize=False, rotate_ligand=False,
-                 exclude_clashes=True, clip=5.0, lib=None):
-        """lib: None -> the product library (GPU); the test-suite passes the emulated one."""
+                 exclude_clashes=True, clip=5.0, lib=None, differentiable=False):
+        """lib: None -> the product library (GPU); the test-suite passes the emulated one.
+        differentiable (a public attribute, as on ``LocalDockingModel``): False -- ``forward`` is the inference path: the
+        correlations carry no graph and the reference's MLP filter runs in the fused kernel.  True -- the model that is
+        trained (the reference trains this model through VolumeConvolution's backward, DockingModels.py:48,71): under
+        autograd, with an input volume or a filter parameter requiring a gradient, the correlations go through the
+        differentiable ``VolumeConvolution`` (csrc/dlpd_corr_grad.h), the filter MODULE is called on the channels-last rows
+        and the nearest upsampling is ``interpolate``; under ``torch.no_grad()`` it takes the fused path like the other."""
         super().__init__()
+        self.differentiable = bool(differentiable)
         self.representation, self.filter = representation, filter
         self.threshold_clash, self.clip = threshold_clash, clip
         self.normalize, self.rotate_ligand, self.exclude = normalize, rotate_ligand, exclude_clashes
@@ -108,8 +118,15 @@ class GlobalDockingModel(nn.Module):
 
     def forward(self, receptor_volumes, ligand_volumes):
         """Lists of (B, C_i, L_i, L_i, L_i) per resolution -> scores (B, 2L_0, 2L_0, 2L_0)."""
-        correlations = [self.convolve(rec, lig) for rec, lig in zip(receptor_volumes, ligand_volumes)]
-        params = mlp_parameters(self.filter)
+        receptor_volumes, ligand_volumes = list(receptor_volumes), list(ligand_volumes)
+        graph = self.differentiable and torch.is_grad_enabled() and (
+            any(v.requires_grad for v in receptor_volumes + ligand_volumes) or
+            (isinstance(self.filter, nn.Module) and any(p.requires_grad for p in self.filter.parameters())))
+        if graph:
+            correlations = [self.convolve(rec, lig) for rec, lig in zip(receptor_volumes, ligand_volumes)]
+        else:       # the inference path: no graph through the correlation, whatever the inputs require
+            correlations = [self.convolve(rec.detach(), lig.detach()) for rec, lig in zip(receptor_volumes, ligand_volumes)]
+        params = None if graph else mlp_parameters(self.filter)
         if params is not None and params[0].shape[0] <= 64 and len(correlations) <= 2:
             W1, b1, W2, b2 = params
             return filter_volumes(correlations, W1, b1, W2, float(b2.reshape(-1)[0]), lib=self._lib)

@@ -28,6 +28,11 @@ SIGNATURES = {
     "dlpd_generic_box_supported": (_i, [_i]),
     "dlpd_correlate_generic_ws_bytes": (_sz, [_i, _i]),
     "dlpd_correlate_generic": (_i, [_p, _p, _p, _i, _i, _i, _f, _p, _p]),
+    "dlpd_correlate_grad_supported": (_i, [_i]),
+    "dlpd_correlate_grad_ws_bytes": (_sz, [_i, _i]),
+    "dlpd_correlate_grad": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "dlpd_correlate_generic_grad_ws_bytes": (_sz, [_i, _i]),
+    "dlpd_correlate_generic_grad": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p]),
     "dlpd_local_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "dlpd_local_max_poses": (_i, [_i, _i]),
     "dlpd_local_correlate": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _ll, _ll, _p]),
@@ -144,7 +149,7 @@ class DlpdLib:
     def call(self, name, *args):
         rc = getattr(self, "_" + name)(*args)
         if SIGNATURES[name][0] is _i and name not in ("dlpd_version", "dlpd_grid_supported", "dlpd_conv3d_supported", "dlpd_orientation_supported",
-                                                      "dlpd_hidden_pad", "dlpd_fused_hidden_pad", "dlpd_generic_box_supported", "dlpd_debug_poison_selfcheck", "dlpd_k1_form_supported", "dlpd_pencil_map_supported", "dlpd_channel_chunks_default", "dlpd_local_max_poses") and rc != 0:
+                                                      "dlpd_hidden_pad", "dlpd_fused_hidden_pad", "dlpd_generic_box_supported", "dlpd_correlate_grad_supported", "dlpd_debug_poison_selfcheck", "dlpd_k1_form_supported", "dlpd_pencil_map_supported", "dlpd_channel_chunks_default", "dlpd_local_max_poses") and rc != 0:
             raise RuntimeError("dlpd: %s failed: %s" % (name, ERRORS.get(rc, rc)))
         return rc
 

@@ -16,6 +16,7 @@
 #include "dlpd_rotate_grad.h"           // ... and the adjoint of the rotation (the ligand's gradient through the poses)
 #include "dlpd_rotate_rgrad.h"          // ... and the rotation's gradient with respect to its matrix (the poses' own gradient)
 #include "dlpd_rotate_shift.h"          // ... and all of them with a per-pose offset of the sample position (sub-voxel translations)
+#include "dlpd_corr_grad.h"             // the adjoint of VolumeConvolution itself (compiled boxes; the plan-free one is below)
 
 #define GEN_MAXN 256                      // box sizes up to 128 (tile: n_in x 64 complex <= 128 KB)
 #define GEN_NACC 4                        // partial sums per output of a direct transform (the final adds are written for 4)
@@ -197,6 +198,57 @@ int dlpd_correlate_generic(const float* v1, const float* v2, float* out, int nvo
   rc = gen_mid(P, Q, nvol, N, N, (long long)N * N, +1, st);
   if (!rc) rc = gen_mid(Q, P, (long long)nvol * N, N, N, N, +1, st);
   if (!rc) rc = gen_last(P, out, (long long)nvol * N * N, N, N, +1, 0, 1, 1.0f / ((float)N * (float)N * (float)N), has_clip, clip, st);
+  if (rc) return rc;
+  return dlpd_check_launch();
+}
+
+// bytes of workspace dlpd_correlate_generic_grad needs for nvol volume pairs of box L
+size_t dlpd_correlate_generic_grad_ws_bytes(int nvol, int L) {
+  if (nvol <= 0 || !dlpd_generic_box_supported(L)) return 0;
+  const size_t N = 2 * (size_t)L;
+  return (size_t)nvol * (3 * N * N * N + (size_t)L * L * N + (size_t)L * N * N) * sizeof(cplx);
+}
+
+// The adjoint of dlpd_correlate_generic (the backward of VolumeConvolution, DockingModels.py:48,71, on a box without a
+// compiled plan): gout (nvol, N^3) f32, v1, v2 (nvol, L^3) f32 -> g1, g2 (nvol, L^3) f32 (csrc/dlpd_corr_grad.h for the
+// formulas); a null g1 / g2 skips that gradient.  The same direct transforms: the FULL forward of gout (n_in = N), the
+// pruned forward of the other volume, the product (without the conjugate for g1), the full inverse, the L^3 corner.
+int dlpd_correlate_generic_grad(const float* gout, const float* v1, const float* v2, float* g1, float* g2, int nvol, int L,
+                                void* ws, void* stream) {
+  if (!gout || !ws || nvol <= 0 || (!g1 && !g2) || (g1 && !v2) || (g2 && !v1)) return DLPD_ERR_ARG;
+  if (!dlpd_generic_box_supported(L)) return DLPD_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int N = 2 * L;
+  const size_t N3 = (size_t)N * N * N;
+  cplx* A = (cplx*)ws;                    // (nvol, N, N, N): the spectrum of gout
+  cplx* B = A + (size_t)nvol * N3;
+  cplx* C = B + (size_t)nvol * N3;
+  cplx* T1 = C + (size_t)nvol * N3;       // (nvol, L, L, N)
+  cplx* T2 = T1 + (size_t)nvol * L * L * N;   // (nvol, L, N, N)
+  size_t nblk = ((size_t)nvol * N3 + 255) / 256;
+  if (nblk > 65536) nblk = 65536;
+  int rc = gen_last(gout, B, (long long)nvol * N * N, N, N, -1, 1, 0, 1.f, 0, 0.f, st);
+  if (!rc) rc = gen_mid(B, C, (long long)nvol * N, N, N, N, -1, st);
+  if (!rc) rc = gen_mid(C, A, nvol, N, N, (long long)N * N, -1, st);
+  for (int which = 0; which < 2 && !rc; which++) {
+    float* out = which ? g2 : g1;
+    if (!out) continue;
+    rc = gen_last(which ? v1 : v2, T1, (long long)nvol * L * L, L, N, -1, 1, 0, 1.f, 0, 0.f, st);
+    if (!rc) rc = gen_mid(T1, T2, (long long)nvol * L, L, N, N, -1, st);
+    if (!rc) rc = gen_mid(T2, B, nvol, L, N, (long long)N * N, -1, st);
+    if (rc) break;
+    if (which) DLPD_LAUNCH(k_gmul_conj, dim3((unsigned)nblk), dim3(256), 0, st, B, (const cplx*)A, (size_t)nvol * N3);   // V1 conj(G)
+    else DLPD_LAUNCH(k_gmul, dim3((unsigned)nblk), dim3(256), 0, st, B, (const cplx*)A, (size_t)nvol * N3);              // G V2
+    rc = gen_mid(B, C, nvol, N, N, (long long)N * N, +1, st);
+    if (!rc) rc = gen_mid(C, B, (long long)nvol * N, N, N, N, +1, st);
+    float* full = (float*)C;                // (nvol, N, N, N) real: C is free again
+    if (!rc) rc = gen_last(B, full, (long long)nvol * N * N, N, N, +1, 0, 1, 1.0f / ((float)N * (float)N * (float)N), 0, 0.f, st);
+    if (rc) break;
+    const size_t n = (size_t)nvol * L * L * L;
+    size_t cblk = (n + 255) / 256;
+    if (cblk > 65536) cblk = 65536;
+    DLPD_LAUNCH(k_gcorner, dim3((unsigned)cblk), dim3(256), 0, st, (const float*)full, out, L, n);
+  }
   if (rc) return rc;
   return dlpd_check_launch();
 }

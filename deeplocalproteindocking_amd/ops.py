@@ -15,8 +15,12 @@ TorchProteinLibrary's volume ops, backed by libdlpd.so.
     ``rotation_grad=True`` differentiates as well -- the three translational degrees of freedom of ``Docker.minimize(translation=True)``.
     ``conv3d_autograd`` is the plugins' stride-1 convolution with both gradients on the HIP kernels
     (``conv3d_input_grad``, ``conv3d_weight_grad``: csrc/dlpd_conv_grad.h); plain ``conv3d`` stays inference only.
+    ``VolumeConvolution`` is differentiable with respect to both volumes wherever it runs (csrc/dlpd_corr_grad.h: the full
+    transform of the incoming gradient, the products with the other volume's spectrum, inverses pruned to the L^3 corner;
+    dlpd_correlate_generic_grad on a box without a compiled plan) -- what ``GlobalDockingModel(differentiable=True)`` trains through.
 
-Everything else is inference only (the docking search runs under torch.no_grad(), local_test.py:67).
+Everything else (the fused filter kernels, the max-pool, the fused search pipeline) is inference only (the docking search
+runs under torch.no_grad(), local_test.py:67).
 Box sizes 32 / 40 / 64 / 80 run the compiled FFT pipeline, any other box (<= 128) a plan-free slow path.
 Build-defined conventions (TPL source absent, parity unpinned): rotation about index L/2 with
 trilinear interpolation and zeros outside; ``clip`` clamps the correlation OUTPUT to +-clip.
@@ -214,6 +218,11 @@ class VolumeConvolution(nn.Module):
         return self.clip if self.clip_mode == "output" else None
 
     def forward(self, input_volume1, input_volume2):
+        """Differentiable with respect to both volumes (first order; csrc/dlpd_corr_grad.h, and dlpd_correlate_generic_grad on
+        a box without a compiled plan): when autograd is enabled and one of them requires a gradient the call is recorded, and
+        only the gradients that are needed are computed.  The forward is the same call either way (the same bits).  With
+        ``clip`` in "output" mode the gradient is zero where the correlation was clamped (|out| >= clip); "input" mode clamps
+        in plain torch before the operator and an embedded box is cut out in plain torch after it: autograd carries both."""
         v1, v2 = _check(input_volume1, "volume1", self.lib), _check(input_volume2, "volume2", self.lib)
         if v1.shape != v2.shape:
             raise RuntimeError("dlpd: VolumeConvolution shape mismatch %s vs %s" % (tuple(v1.shape), tuple(v2.shape)))
@@ -222,9 +231,12 @@ class VolumeConvolution(nn.Module):
             v1, v2 = v1.clamp(-c, c), v2.clamp(-c, c)
         B, C, L = v1.shape[0], v1.shape[1], v1.shape[2]
         lib = self.lib or get_lib()
+        graph = torch.is_grad_enabled() and (v1.requires_grad or v2.requires_grad)
         if not lib.call("dlpd_grid_supported", L):
             Lc = next((c for c in (32, 40, 64, 80) if c > L and lib.call("dlpd_grid_supported", c)), None) if self.embed else None
             if Lc is None:
+                if graph:
+                    return _VolumeConvolve.apply(v1, v2, self, lib, False)
                 return self._forward_generic(v1, v2, lib)
             # the L^3 volumes in the corner of the next compiled box: the correlation of two L-sized volumes is linear
             # for every |t| < L on any grid of >= 2L points, so the (2L)^3 result sits inside the (2Lc)^3 one at index t
@@ -234,6 +246,12 @@ class VolumeConvolution(nn.Module):
             big = self.forward(e1, e2)
             idx = torch.tensor(list(range(0, L + 1)) + list(range(2 * Lc - (L - 1), 2 * Lc)), dtype=torch.long, device=v1.device)
             return big.index_select(2, idx).index_select(3, idx).index_select(4, idx).contiguous()
+        if graph:
+            return _VolumeConvolve.apply(v1, v2, self, lib, True)
+        return self._forward_compiled(v1, v2, lib)
+
+    def _forward_compiled(self, v1, v2, lib):
+        B, C, L = v1.shape[0], v1.shape[1], v1.shape[2]
         N, NZ, nvol = 2 * L, L + 1, B * C
         dev, st = v1.device, _stream(v1.device)
         wsA = torch.empty(nvol * NZ * L * L * 2, dtype=torch.float32, device=dev)
@@ -269,6 +287,77 @@ def _vc_generic(self, v1, v2, lib):
 
 
 VolumeConvolution._forward_generic = _vc_generic
+
+CORR_GRAD_WS_BYTES = 2 << 30        # cap of the backward's scratch (workspace and the two spectra): volumes go in chunks that fit it
+
+
+def _vc_grad(lib, g, v1, v2, want1, want2, compiled, chunk=None):
+    """The two input gradients of VolumeConvolution for the incoming gradient ``g`` (B, C, N, N, N), contiguous: (g1, g2), None
+    for one that is not wanted -- its kernels are not launched, its output pointer is null.  compiled: dlpd_correlate_grad with
+    the spectra of the volumes recomputed here by dlpd_rfft3d_padded(scale = 1) (none is kept alive between forward and
+    backward); otherwise dlpd_correlate_generic_grad.  ``chunk``: volumes per call (None: what keeps the scratch below
+    ``CORR_GRAD_WS_BYTES``); the volumes are independent, so the bits do not depend on it."""
+    B, C, L = v1.shape[0], v1.shape[1], v1.shape[2]
+    N, NZ, nvol = 2 * L, L + 1, B * C
+    dev, st = v1.device, _stream(v1.device)
+    g1 = torch.empty_like(v1) if want1 else None
+    g2 = torch.empty_like(v2) if want2 else None
+    spec_bytes = NZ * N * N * 8
+    if compiled:
+        per = lib.call("dlpd_correlate_grad_ws_bytes", 1, L)
+        if per == 0:
+            raise RuntimeError("dlpd: no VolumeConvolution backward kernel for box %d" % L)
+        most = max(1, CORR_GRAD_WS_BYTES // (per + (want1 + want2) * spec_bytes + NZ * L * L * 8))
+    else:
+        per = lib.call("dlpd_correlate_generic_grad_ws_bytes", 1, L)
+        if per == 0:
+            raise RuntimeError("dlpd: VolumeConvolution box size %d exceeds the generic path (box <= 128)" % L)
+        most = max(1, min((4 << 30) // per, 65535 // N))
+    chunk = max(1, min(nvol, most if chunk is None else int(chunk)))
+    ws = torch.empty(per * chunk, dtype=torch.uint8, device=dev)
+    if compiled:
+        wsA = torch.empty(chunk * NZ * L * L * 2, dtype=torch.float32, device=dev)
+        spec1 = torch.empty(chunk * spec_bytes, dtype=torch.uint8, device=dev) if want2 else None      # (g2 reads V1, g1 reads V2)
+        spec2 = torch.empty(chunk * spec_bytes, dtype=torch.uint8, device=dev) if want1 else None
+    vol, big = 4 * L ** 3, 4 * N ** 3
+    for beg in range(0, nvol, chunk):
+        n = min(chunk, nvol - beg)
+        p1, p2 = (_ptr(g1) + vol * beg) if want1 else None, (_ptr(g2) + vol * beg) if want2 else None
+        if compiled:
+            if want2:
+                lib.call("dlpd_rfft3d_padded", _ptr(v1) + vol * beg, _ptr(spec1), _ptr(wsA), n, L, 1.0, st)
+            if want1:
+                lib.call("dlpd_rfft3d_padded", _ptr(v2) + vol * beg, _ptr(spec2), _ptr(wsA), n, L, 1.0, st)
+            lib.call("dlpd_correlate_grad", _ptr(g) + big * beg, _ptr(spec1) or None, _ptr(spec2) or None, p1, p2, _ptr(ws), n, L, st)
+        else:
+            lib.call("dlpd_correlate_generic_grad", _ptr(g) + big * beg, _ptr(v1) + vol * beg, _ptr(v2) + vol * beg, p1, p2, n, L,
+                     _ptr(ws), st)
+    return g1, g2
+
+
+class _VolumeConvolve(torch.autograd.Function):
+    """VolumeConvolution under autograd: the forward is the plain call (compiled box or plan-free), the backward ``_vc_grad``
+    for the inputs that need a gradient.  Saved: the two inputs, and the output where it was clamped (the clamp's mask)."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, lib, compiled):
+        a, b = v1.detach(), v2.detach()
+        out = op._forward_compiled(a, b, lib) if compiled else op._forward_generic(a, b, lib)
+        clip = op.out_clip
+        ctx.save_for_backward(v1, v2, *((out,) if clip is not None else ()))
+        ctx.args = (lib, op.lib, compiled, clip)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        v1, v2 = ctx.saved_tensors[0].detach(), ctx.saved_tensors[1].detach()
+        lib, given, compiled, clip = ctx.args
+        g = _check(gout, "the gradient", given)                # (contiguous: out.sum().backward() hands in an expanded tensor)
+        if clip is not None:
+            g = g * (ctx.saved_tensors[2].abs() < float(clip)).to(g.dtype)
+        g1, g2 = _vc_grad(lib, g, v1, v2, ctx.needs_input_grad[0], ctx.needs_input_grad[1], compiled)
+        return g1, g2, None, None, None
 
 
 def filter_volumes(conv_list, W1, b1, W2, b2, mask_norm=None, threshold=0.0, lib=None):

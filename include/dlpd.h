@@ -263,6 +263,23 @@ size_t dlpd_correlate_generic_ws_bytes(int nvol, int L);
 int dlpd_correlate_generic(const float* v1, const float* v2, float* out, int nvol, int L, int has_clip, float clip,
                            void* ws, void* stream);
 
+/* The BACKWARD of VolumeConvolution (the reference trains GlobalDockingModel through it: DockingModels.py:48,71) for an
+ * incoming gradient gout (nvol, N^3) over the whole grid:
+ *   g1[s] = sum_r gout[(s - r) mod N] v2[r],  g2[r] = sum_s gout[(s - r) mod N] v1[s],  both (nvol, L^3), s, r in [0, L)^3.
+ * Compiled boxes (dlpd_correlate_grad_supported(L): the boxes of dlpd_grid_supported): spec1, spec2 (nvol, NZ, N, N) are
+ * dlpd_rfft3d_padded(scale = 1) of v1, v2; ws: dlpd_correlate_grad_ws_bytes(nvol, L) bytes of scratch.  A null g1 / g2 skips
+ * that gradient, and the spectrum only it reads (spec2 for g1, spec1 for g2) may then be null too.  No atomics: the same
+ * bits on every run. */
+int dlpd_correlate_grad_supported(int L);
+size_t dlpd_correlate_grad_ws_bytes(int nvol, int L);
+int dlpd_correlate_grad(const float* gout, const void* spec1, const void* spec2, float* g1, float* g2, void* ws, int nvol,
+                        int L, void* stream);
+/* ... and of dlpd_correlate_generic (DockingModels.py:48,71 on a box without a compiled plan, Docker.py:18): the same
+ * gradients from the volumes themselves, by the direct transforms, L <= 128.  ws: dlpd_correlate_generic_grad_ws_bytes. */
+size_t dlpd_correlate_generic_grad_ws_bytes(int nvol, int L);
+int dlpd_correlate_generic_grad(const float* gout, const float* v1, const float* v2, float* g1, float* g2, int nvol, int L,
+                                void* ws, void* stream);
+
 /* LOCAL DOCKING -- MultiplyVolumes (src/Models/MultiplyVolumes.py:13-60) under a rotation, LocalDockingModel.forward
  * (src/Models/DockingModels.py:102-120; caller LocalTrainer.score, src/Training/LocalTrainer.py:146-177): the per-channel
  * correlation of the receptor with a ligand under an ARBITRARY rotation at a HANDFUL of translations, by direct summation.
