@@ -13,15 +13,17 @@ be ANY module mapping (voxels, channels) -> (voxels, 1) (DockingModels.py:82): a
 that MLP is called on the reference's own channels-last layout.
 ``GlobalDockingModel(differentiable=True)`` is the model that is trained: under autograd its correlations are the
 differentiable ``VolumeConvolution`` (the adjoint FFT kernels of csrc/dlpd_corr_grad.h) and its filter is called, so a loss
-over the whole (2L)^3 translation grid reaches the filter's and the representation's parameters.
+over the whole (2L)^3 translation grid reaches the filter's and the representation's parameters.  With ``fused_filter_grad=True``
+as well, the reference's MLP filter is not called there either: it runs as ``ops.filter_volumes_autograd``, the inference
+kernel with the backward kernel of csrc/dlpd_filter_grad.h.
 """
 import os
 
 import torch
 from torch import nn
 
-from deeplocalproteindocking_amd.ops import (MultiplyVolumes, VolumeConvolution, VolumeRotation, filter_volumes,
-                                             local_correlate_rotated, local_filter)
+from deeplocalproteindocking_amd.ops import (MultiplyVolumes, VolumeConvolution, VolumeRotation, filter_grad_supported,
+                                             filter_volumes, filter_volumes_autograd, local_correlate_rotated, local_filter)
 from deeplocalproteindocking_amd.Utils.Conventions import rotation_pivot
 
 
@@ -66,6 +68,17 @@ def mlp_parameters(filt):
     return None
 
 
+def live_mlp_parameters(filt):
+    """The test of ``mlp_parameters`` with the LIVE parameters (W1, b1, W2, b2) of ``fc[0]`` / ``fc[2]``, for the filter kernel
+    that has a backward (ops.filter_volumes_autograd); None for any other module."""
+    fc = getattr(filt, "fc", None)
+    if (type(filt).__name__ == "SimpleFilter" and isinstance(fc, nn.Sequential) and len(fc) == 3
+            and isinstance(fc[0], nn.Linear) and isinstance(fc[1], nn.ReLU) and isinstance(fc[2], nn.Linear)
+            and fc[2].out_features == 1 and fc[0].bias is not None and fc[2].bias is not None):
+        return fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias
+    return None
+
+
 def fused_filter_parameters(model):
     """Filter parameters when ``model(receptor_volumes, ligand_volumes)`` (Docker.py:229) IS the
     reference's ``GlobalDockingModel.forward`` (DockingModels.py:63-84: per-channel correlation,
@@ -88,16 +101,22 @@ class GlobalDockingModel(nn.Module):
     FILES = ("%s_repr_epoch%d.th", "%s_filter_epoch%d.th")
 
     def __init__(self, representation, filter, threshold_clash=300, normalize=False, rotate_ligand=False,
-                 exclude_clashes=True, clip=5.0, lib=None, differentiable=False):
+                 exclude_clashes=True, clip=5.0, lib=None, differentiable=False, fused_filter_grad=False):
         """lib: None -> the product library (GPU); the test-suite passes the emulated one.
         differentiable (a public attribute, as on ``LocalDockingModel``): False -- ``forward`` is the inference path: the
         correlations carry no graph and the reference's MLP filter runs in the fused kernel.  True -- the model that is
         trained (the reference trains this model through VolumeConvolution's backward, DockingModels.py:48,71): under
         autograd, with an input volume or a filter parameter requiring a gradient, the correlations go through the
         differentiable ``VolumeConvolution`` (csrc/dlpd_corr_grad.h), the filter MODULE is called on the channels-last rows
-        and the nearest upsampling is ``interpolate``; under ``torch.no_grad()`` it takes the fused path like the other."""
+        and the nearest upsampling is ``interpolate``; under ``torch.no_grad()`` it takes the fused path like the other.
+        fused_filter_grad (a public attribute, opt-in as ``hip_autograd`` is on the plugins): True -- where ``forward`` builds a
+        graph and the filter is the reference's MLP on one or two resolutions the backward kernel supports
+        (``ops.filter_grad_supported``), the filter stage is ``ops.filter_volumes_autograd`` on the live ``fc[0]`` / ``fc[2]``
+        parameters: the inference kernel forward, csrc/dlpd_filter_grad.h backward, no interpolate / cat / permute and no saved
+        activations.  Any other filter or shape is called as a module, as with False."""
         super().__init__()
         self.differentiable = bool(differentiable)
+        self.fused_filter_grad = bool(fused_filter_grad)
         self.representation, self.filter = representation, filter
         self.threshold_clash, self.clip = threshold_clash, clip
         self.normalize, self.rotate_ligand, self.exclude = normalize, rotate_ligand, exclude_clashes
@@ -126,6 +145,13 @@ class GlobalDockingModel(nn.Module):
             correlations = [self.convolve(rec, lig) for rec, lig in zip(receptor_volumes, ligand_volumes)]
         else:       # the inference path: no graph through the correlation, whatever the inputs require
             correlations = [self.convolve(rec.detach(), lig.detach()) for rec, lig in zip(receptor_volumes, ligand_volumes)]
+        if graph and self.fused_filter_grad and 1 <= len(correlations) <= 2:
+            live = live_mlp_parameters(self.filter)
+            fine, coarse = correlations[0], (correlations[1] if len(correlations) == 2 else None)
+            if live is not None and live[0].shape[1] == sum(c.shape[1] for c in correlations) and filter_grad_supported(
+                    fine.shape[1], fine.shape[2], 0 if coarse is None else coarse.shape[1],
+                    0 if coarse is None else coarse.shape[2], live[0].shape[0], self._lib):
+                return filter_volumes_autograd(correlations, *live, lib=self._lib)
         params = None if graph else mlp_parameters(self.filter)
         if params is not None and params[0].shape[0] <= 64 and len(correlations) <= 2:
             W1, b1, W2, b2 = params

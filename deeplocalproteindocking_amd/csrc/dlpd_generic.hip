@@ -17,6 +17,7 @@
 #include "dlpd_rotate_rgrad.h"          // ... and the rotation's gradient with respect to its matrix (the poses' own gradient)
 #include "dlpd_rotate_shift.h"          // ... and all of them with a per-pose offset of the sample position (sub-voxel translations)
 #include "dlpd_corr_grad.h"             // the adjoint of VolumeConvolution itself (compiled boxes; the plan-free one is below)
+#include "dlpd_filter_grad.h"           // the adjoint of the per-voxel filter over the correlations (global training)
 
 #define GEN_MAXN 256                      // box sizes up to 128 (tile: n_in x 64 complex <= 128 KB)
 #define GEN_NACC 4                        // partial sums per output of a direct transform (the final adds are written for 4)

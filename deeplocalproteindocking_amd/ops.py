@@ -18,8 +18,12 @@ TorchProteinLibrary's volume ops, backed by libdlpd.so.
     ``VolumeConvolution`` is differentiable with respect to both volumes wherever it runs (csrc/dlpd_corr_grad.h: the full
     transform of the incoming gradient, the products with the other volume's spectrum, inverses pruned to the L^3 corner;
     dlpd_correlate_generic_grad on a box without a compiled plan) -- what ``GlobalDockingModel(differentiable=True)`` trains through.
+    ``filter_volumes_autograd`` is the grid filter (nearest upsample + concat + MLP over the correlations) with a graph: the
+    inference kernel forward, one fused backward kernel for the correlations' and the four parameters' gradients
+    (csrc/dlpd_filter_grad.h: the hidden layer recomputed, f32 matrix cores, fixed-order sums); plain ``filter_volumes`` and the
+    clash mask stay inference only.  ``GlobalDockingModel(fused_filter_grad=True)`` uses it.
 
-Everything else (the fused filter kernels, the max-pool, the fused search pipeline) is inference only (the docking search
+Everything else (the filter fused into the search pipeline, the max-pool, the fused search pipeline) is inference only (the docking search
 runs under torch.no_grad(), local_test.py:67).
 Box sizes 32 / 40 / 64 / 80 run the compiled FFT pipeline, any other box (<= 128) a plan-free slow path.
 Build-defined conventions (TPL source absent, parity unpinned): rotation about index L/2 with
@@ -382,6 +386,88 @@ def filter_volumes(conv_list, W1, b1, W2, b2, mask_norm=None, threshold=0.0, lib
     (lib or get_lib()).call("dlpd_filter_mask", _ptr(c0), C0, N0, _ptr(c1), C1, N1, _ptr(mask_norm), float(threshold),
                    int(has_clash), _ptr(W1t), _ptr(b1), _ptr(W2), float(b2), H, _ptr(V), B, _stream(dev))
     return V
+
+
+def filter_grad_supported(C0, N0, C1, N1, H, lib=None):
+    """True where the filter's backward kernel (csrc/dlpd_filter_grad.h) exists for conv0 (B, C0, N0^3), conv1 (B, C1, N1^3)
+    and hidden width H."""
+    return bool((lib or get_lib()).call("dlpd_filter_grad_supported", int(C0), int(N0), int(C1), int(N1), int(H)))
+
+
+def _filter_shapes(conv_list):
+    if not 1 <= len(conv_list) <= 2:
+        raise RuntimeError("dlpd: one or two resolutions are supported")
+    c0 = conv_list[0]
+    c1 = conv_list[1] if len(conv_list) == 2 else None
+    return (c0.shape[1], c0.shape[2]) + ((c1.shape[1], c1.shape[2]) if c1 is not None else (0, 0))
+
+
+class _FilterVolumes(torch.autograd.Function):
+    """filter_volumes under autograd: the forward is the inference kernel (no clash mask), the backward ONE dlpd_filter_grad
+    call for the gradients that are asked for.  Saved: the correlations and the four parameters -- `pre` is recomputed."""
+
+    @staticmethod
+    def forward(ctx, c0, c1, W1, b1, W2, b2, lib):
+        convs = [c0.detach()] + ([c1.detach()] if c1 is not None else [])
+        V = filter_volumes(convs, W1.detach(), b1.detach(), W2.detach(), float(b2.detach().reshape(-1)[0]), lib=lib)
+        ctx.save_for_backward(c0, W1, b1, W2, b2, *((c1,) if c1 is not None else ()))
+        ctx.lib = lib
+        return V
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        c0, W1, b1, W2, b2 = (t.detach() for t in ctx.saved_tensors[:5])
+        c1 = ctx.saved_tensors[5].detach() if len(ctx.saved_tensors) == 6 else None
+        given = ctx.lib
+        lib = given or get_lib()
+        g = _check(gout, "the gradient", given)                # (contiguous: V.sum().backward() hands in an expanded tensor)
+        need = ctx.needs_input_grad
+        B, C0, N0 = c0.shape[0], c0.shape[1], c0.shape[2]
+        C1, N1 = (c1.shape[1], c1.shape[2]) if c1 is not None else (0, 0)
+        H, C, dev = W1.shape[0], C0 + C1, c0.device
+        W1t = W1.to(dev, torch.float32).t().contiguous()       # (C, H), as the forward passes it
+        b1c = b1.to(dev, torch.float32).contiguous()
+        W2c = W2.to(dev, torch.float32).reshape(-1).contiguous()
+        g0 = torch.empty_like(c0) if need[0] else None
+        g1 = torch.empty_like(c1) if (c1 is not None and need[1]) else None
+        want_params = any(need[2:6])
+        gp = ws = None
+        if want_params:
+            gp = torch.empty(C * H + 2 * H + 1, dtype=torch.float32, device=dev)
+            ws = torch.empty(lib.call("dlpd_filter_grad_ws_bytes", C0, N0, C1, N1, H, B), dtype=torch.uint8, device=dev)
+        if g0 is not None or g1 is not None or want_params:
+            lib.call("dlpd_filter_grad", _ptr(g), _ptr(c0), C0, N0, _ptr(c1), C1, N1, _ptr(W1t), _ptr(b1c), _ptr(W2c), H,
+                     _ptr(g0), _ptr(g1), _ptr(gp), _ptr(ws), B, _stream(dev))
+        gW1 = gb1 = gW2 = gb2 = None
+        if want_params:
+            if need[2]:
+                gW1 = gp[:C * H].reshape(C, H).t().to(W1).contiguous()
+            if need[3]:
+                gb1 = gp[C * H:C * H + H].to(b1).clone()
+            if need[4]:
+                gW2 = gp[C * H + H:C * H + 2 * H].to(W2).reshape(W2.shape).clone()
+            if need[5]:
+                gb2 = gp[C * H + 2 * H:].to(b2).reshape(b2.shape).clone()
+        return g0, g1, gW1, gb1, gW2, gb2, None
+
+
+def filter_volumes_autograd(conv_list, W1, b1, W2, b2, lib=None):
+    """``filter_volumes`` (no clash mask) with a graph: conv_list as there, the parameters as ``nn.Linear`` holds them -- W1 (H, C),
+    b1 (H), W2 (1, H), b2 (1), live tensors -- -> V (B, N0, N0, N0), the bits of ``filter_volumes``.  The backward is the fused
+    kernel of csrc/dlpd_filter_grad.h: the gradients of the correlations and of the four parameters that are asked for, from one
+    call that recomputes the hidden layer (first order only).  RuntimeError where the kernel does not exist
+    (``filter_grad_supported``)."""
+    conv_list = list(conv_list)
+    C0, N0, C1, N1 = _filter_shapes(conv_list)
+    H = W1.shape[0]
+    if W1.dim() != 2 or W1.shape[1] != C0 + C1 or b1.numel() != H or W2.numel() != H or b2.numel() != 1:
+        raise RuntimeError("dlpd: filter parameters do not match the correlations: W1 (H, C0 + C1), b1 (H), W2 (1, H), b2 (1)")
+    if not filter_grad_supported(C0, N0, C1, N1, H, lib):
+        raise RuntimeError("dlpd: no filter backward kernel for %d @ %d^3 + %d @ %d^3, hidden width %d" % (C0, N0, C1, N1, H))
+    c0 = _check(conv_list[0], "conv0", lib)
+    c1 = _check(conv_list[1], "conv1", lib) if len(conv_list) == 2 else None
+    return _FilterVolumes.apply(c0, c1, W1, b1, W2, b2, lib)
 
 
 def conv3d_supported(weight, D, lib=None):

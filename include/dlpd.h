@@ -370,6 +370,23 @@ int dlpd_filter_mask(const float* conv0, int C0, int N0, const float* conv1, int
                      const float* mask_norm, float thr, int has_clash, const float* W1t, const float* b1,
                      const float* W2, float b2, int H, float* V, int nb, void* stream);
 
+/* The BACKWARD of that filter without the clash mask (the reference trains GlobalDockingModel's filter through torch's
+ * interpolate / cat / permute / Linear / ReLU / Linear, DockingModels.py:74-83) for an incoming gradient g (nb, N0^3):
+ *   pre_j = b1_j + sum_c W1[j,c] x_c is recomputed per fine voxel (x: the conv0 channels, then the conv1 channels at the
+ *   coarse parent), delta_j = g W2_j [pre_j > 0];
+ *   gconv0 (nb, C0, N0^3) = sum_j W1[j,c] delta_j;   gconv1 (nb, C1, N1^3) the same over the fine children of a coarse voxel;
+ *   gparams = [gW1t (C x H) | gb1 (H) | gW2 (H) | gb2 (1)], sums over all nb N0^3 voxels, C = C0 + C1.
+ * An output whose pointer is null is not computed (ws may be null without gparams).  Nothing is saved by the forward: the
+ * inputs are all it reads.  Supported (the _supported call; DLPD_ERR_UNSUPPORTED otherwise): 1 <= H <= 64, C0 >= 1, C1 = 0
+ * or N1 = N0 or N1 = N0 / 2 with N0 even, C0 + C1 <= 128, any N0 >= 2.  The voxels are split over a number of blocks that
+ * depends on the shape alone, each writes its partial gparams to ws (the _ws_bytes call) and the partials are added in
+ * ascending order in float64: no float atomics, the same bits on every run and device. */
+int dlpd_filter_grad_supported(int C0, int N0, int C1, int N1, int H);
+size_t dlpd_filter_grad_ws_bytes(int C0, int N0, int C1, int N1, int H, int nb);
+int dlpd_filter_grad(const float* g, const float* conv0, int C0, int N0, const float* conv1, int C1, int N1,
+                     const float* W1t, const float* b1, const float* W2, int H, float* gconv0, float* gconv1,
+                     float* gparams, void* ws, int nb, void* stream);
+
 /* Same with strided layouts and weights padded to HP = dlpd_hidden_pad(H): 4 voxels per thread,
  * float4 traffic.  conv0 (nb, *, N0^3) uses its first C0 channels (batch stride conv0_bstride);
  * mask_norm has batch stride mask_bstride (so it may be a channel of conv0).
