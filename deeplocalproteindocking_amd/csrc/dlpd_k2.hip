@@ -38,7 +38,18 @@
 // adjacent output pairs (16 bytes) and the 8 lanes of a pencil with a full 128-byte line: the rows go to global
 // memory from the butterfly registers, without the copy-out trip through the slab (2.84 -> 2.74 ms).  The same
 // idea with the standard dealing and a DPP lane-pair exchange was slower (3.02 vs 2.78 ms: the exchange is VALU).
+// SET PING-PONG (shared receptor, rec_bstride == 0: the search).  A wave's two column sets, w and w + W, are independent, so
+// the order in which it visits them changes no bit.  Even rotations of a block's part visit w then w + W, odd ones
+// w + W then w: the receptor values of a rotation's second set are still in registers when the next rotation starts
+// with that same set, and each rotation fetches ONE set's receptor values (16 loads per lane) instead of two.  With a
+// receptor per rotation (rec_bstride != 0) nothing can be kept: fixed order, two fetches.  The two column passes of a
+// rotation are written out (not a loop of two): the first has no receptor request and rv is dead from its multiply on.
+// -DDLPD_K2_SET_PINGPONG=0: the loop over the two sets as it was, behind the per-set lambda (fixed order, two fetches; the
+// bit-equality reference of tests/test_k2_set_order_gpu.py and the A/B baseline).  EXPERIMENTS.md, section K2-SETORDER.
 // ------------------------------------------------------------------------------------------
+#ifndef DLPD_K2_SET_PINGPONG
+#define DLPD_K2_SET_PINGPONG 1
+#endif
 #ifdef DLPD_STAMPS
 __device__ unsigned long long dlpd_stamps_k2[16];
 extern "C" int dlpd_debug_read_stamps_k2(unsigned long long* host16) {
@@ -201,6 +212,8 @@ k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __rest
         for (int q = 0; q < R2; q++) rv[i][q] = rbase[(unsigned)(idx.out_index(i, q, tc) * N) + (unsigned)col];
       }
   };
+  // SET PING-PONG: one receptor fetch per rotation where the batch shares the receptor (block-uniform)
+  const bool pingpong = DLPD_K2_SET_PINGPONG && MODE == 1 && rec_bstride == 0;
   fetch_rows(b_beg);
   if (MODE == 1) fetch_rec(b_beg, wave);
   __syncthreads();                                         // twiddle table visible
@@ -213,14 +226,14 @@ k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __rest
     __syncthreads();                                       // all rows y-transformed (and the previous slab copied out)
     DLPD_STAMP(1);
     // ---- columns: forward x, receptor multiply, inverse x -- all inside one wave per set
-#pragma unroll 1
-    for (int set = wave; set < NSET; set += W) {
+    const int par = pingpong ? (b - b_beg) & 1 : 0;        // odd rotations of a part visit wave + W first
+    // one column set.  request: this set's receptor values are requested here, before its first x pass; otherwise rv
+    // holds them already
+    auto column_pass = [&](const int set, const bool request) {
       const int col = set * 8 + c8;
       const ColAddrG<RS, GS, GX> ad = {slab_swz(col)};
       const int tc = lane >> 3;
-      // receptor values: the first set's were requested in the row phase (ahead of the second row set's output
-      // stores), the second set's are requested here, before its first x pass
-      if (MODE == 1 && set != wave) fetch_rec(b, set);
+      if (MODE == 1 && request) fetch_rec(b, set);
       // first passes leave their outputs in blocks R1 + 1 rows apart (FftPassW::store_blk), the second passes read them there
       const ColMid<RS, R1 + 1> md = {ad.base};
       {
@@ -279,16 +292,29 @@ k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __rest
         DLPD_WAVE_SYNC();
         ps.store(S, ad, tc);
       }
-    }
+    };
+#if DLPD_K2_SET_PINGPONG == 0
+#pragma unroll 1
+    for (int set = wave; set < NSET; set += W) column_pass(set, set != wave);
+#else
+    // The two passes written out.  The first multiplies with what rv holds: with the ping-pong the values of the previous
+    // rotation's second set (before the loop: set `wave` of b_beg), with a receptor per rotation those requested in the
+    // row phase.  The second requests its own before its first x pass and, with the ping-pong, keeps them in rv through
+    // the row phase for the next rotation, which starts with that set.
+    column_pass(wave + (par ? W : 0), false);
+    column_pass(wave + (par ? 0 : W), true);
+#endif
     DLPD_STAMP(3);
     __syncthreads();                                       // all columns done
     DLPD_STAMP(1);
     // ---- the wave's own rows from here to the next column phase.  Order (vmcnt counts loads and stores together, in
     // issue order): next rotation's A rows requested; y-inverse + output of row set w; staging + y-forward of the next
-    // slab's rows 8w.. (the wait for the A rows has only set w's stores behind it); the receptor values of the next
-    // column phase's first set requested; y-inverse + output of row set w + W.  No load is ever waited for behind
-    // stores younger than one transform phase: with all stores ahead of the receptor loads the column phase used to
-    // wait for the write-back of the whole slab (A loads 0.25 ms, receptor loads 0.15 ms of 2.56: variant builds).
+    // slab's rows 8w.. (the wait for the A rows has only set w's stores behind it); with a receptor per rotation, the
+    // receptor values of the next column phase's first set requested; y-inverse + output of row set w + W.  No load is
+    // ever waited for behind stores younger than one transform phase: with all stores ahead of the receptor loads the
+    // column phase used to wait for the write-back of the whole slab (A loads 0.25 ms, receptor loads 0.15 ms of 2.56:
+    // variant builds).  The ping-pong issues no receptor load here: its one request per rotation is the second column
+    // pass' own, which sits behind the previous row phase's 16 output stores of row set w + W, as that request always did.
     auto inverse_rows_out = [&](int set) {
       if (MODE == 1) {
         const RowAddr<RS> ad = {rb(set * 8 + qr)};
@@ -337,7 +363,7 @@ k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __rest
       DLPD_STAMP(0);
       forward_rows();
       DLPD_STAMP(2);
-      if (MODE == 1) fetch_rec(b + 1, wave);
+      if (MODE == 1 && !pingpong) fetch_rec(b + 1, wave);
     }
     inverse_rows_out(wave + W);
   }
