@@ -1269,7 +1269,9 @@ class Docker:
                 ligand = be.project(lc, ln, lo, L, self.resolution, dev, R=Rb, shift=self.box_center,
                                     cells=bool(getattr(self, "_project_cells", False)))
                 # the forbidden volume = the sum over the atom types (Docker.py:169): projected once more with the types summed in
-                # the accumulator (33 MB; exact) instead of a pass over the eleven volumes
+                # the accumulator (33 MB) instead of a pass over the eleven volumes -- the integer sum of the types' fixed-point
+                # densities converted once: equal to it bit for bit while every type stays below 4 per voxel (accumulator < 2^24,
+                # each type's own float conversion is exact); above that the two differ by float32 rounding of either
                 ligand.dlpd_type_sum = be.project(lc, ln, lo, L, self.resolution, dev, R=Rb, shift=self.box_center, sum_types=True)[:, 0]
                 return ligand, model.representation(ligand)
 

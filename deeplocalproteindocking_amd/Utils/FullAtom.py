@@ -218,7 +218,8 @@ class CoordsBackend:
     def project(self, coords, num_atoms_of_type, offsets, box_size, resolution, device, R=None, shift=None,
                 sum_types=False, lib=None, cells=False):
         """coords (B or 1, 3*Nmax); R (nb,3,3) f32 device -> one volume set per rotation of the
-        SAME atoms (B must be 1 then).  Returns (nb, 11 or 1, L, L, L) float32 on ``device``.
+        SAME atoms (B = 1), or of its own row (B = nb); any other B, and a ``shift`` that does not hold exactly three
+        values, raise ValueError before anything is launched.  Returns (nb, 11 or 1, L, L, L) float32 on ``device``.
         cells (all types only): the CELL-WISE projection -- only the 4 x 4 x 4 cells the atoms' windows reach are cleared,
         accumulated and converted; the result carries their map (``.dlpd_occupancy``, uint8 (nb, ceil(L/4)^3)) and is NOT
         WRITTEN elsewhere (``.dlpd_unwritten``): for consumers that go by the map (the E3 plugin inside outputs_with_maps)."""
@@ -232,10 +233,18 @@ class CoordsBackend:
         stride = c.shape[1] // 3
         if R is not None:
             nb = R.shape[0]
+            if c.shape[0] not in (1, nb):       # (the kernel reads nb * stride atoms)
+                raise ValueError("dlpd: project got %d rotations for coords of %d rows; the rows must be 1 or one per rotation"
+                                 % (nb, c.shape[0]))
             if c.shape[0] == 1 and nb > 1:
                 c, nt, of = c.expand(nb, -1).contiguous(), nt.expand(nb, -1).contiguous(), of.expand(nb, -1).contiguous()
             R = R.to(device=device, dtype=torch.float32).contiguous()
-        sx, sy, sz = (0.0, 0.0, 0.0) if shift is None else [float(v) for v in torch.as_tensor(shift).reshape(-1)[:3]]
+        sx, sy, sz = 0.0, 0.0, 0.0
+        if shift is not None:
+            shift = torch.as_tensor(shift)
+            if shift.numel() != 3:              # (one shift for all rows; more values would be dropped silently)
+                raise ValueError("dlpd: project takes one shift of three values, got shape %s" % (tuple(shift.shape),))
+            sx, sy, sz = [float(v) for v in shift.reshape(-1)]
         nch = 1 if sum_types else NUM_ATOM_TYPES
         out = torch.empty(nb, nch, box_size, box_size, box_size, dtype=torch.float32, device=device)
         if cells:
