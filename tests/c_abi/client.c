@@ -5,12 +5,15 @@
  *   client <library.so> hip       libdlpd.so on an MI355X: buffers come from hipMalloc (libamdhip64 is dlopen'ed here,
  *                                 so this file needs no HIP header)
  *
- * It runs three entry points whose results can be checked without an oracle:
+ * It runs four entry points whose results can be checked without an oracle:
  *   1. dlpd_rotate_trilinear with the identity rotation returns the volume itself, bit for bit   (Docker.py:218)
  *   2. dlpd_topk_select on a volume with known minima returns them in the reference's pick order (Docker.py:89-98)
  *   3. dlpd_rfft3d_padded + dlpd_zfft + dlpd_xy_correlate + dlpd_zifft_real of a volume with a one-voxel volume at
  *      (1,2,3): the circular cross-correlation on the 2L grid is the volume shifted by (-1,-2,-3)  (DockingModels.py:71,
  *      MultiplyVolumes.py:13-47)
+ *   4. dlpd_score_rotations, the one-call K1 + K2 + K3 driver, with the identity rotation, the same one-voxel volume as the
+ *      ligand and a probe filter (W1 = [1; -1], W2 = [1, -1], no bias: relu(x) - relu(-x) = x) returns that same shifted volume
+ *      over the whole 2L grid  (Docker.py:211-232)
  * and prints "c-abi client ok" (exit code 0) or the first mismatch (exit code 1). */
 #include <dlfcn.h>
 #include <math.h>
@@ -50,6 +53,9 @@ typedef int (*dlpd_rfft3d_padded_t)(const float*, void*, void*, int, int, float,
 typedef int (*dlpd_zfft_t)(const float*, const float*, void*, int, int, int, long long, int, float, void*);
 typedef int (*dlpd_xy_correlate_t)(const void*, const void*, void*, int, int, int, long long, void*);
 typedef int (*dlpd_zifft_real_t)(const void*, float*, int, int, int, int, float, void*);
+typedef int (*dlpd_hidden_pad_t)(int);
+typedef int (*dlpd_score_rotations_t)(const float*, const void*, const float*, int, int, int, int, float, const float*, const float*,
+                                      const float*, float, int, int, float, float, void*, void*, float*, void*);
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: client <library.so> host|hip\n"); return 2; }
@@ -68,9 +74,10 @@ int main(int argc, char** argv) {
   dlpd_version_t dlpd_version_fn; dlpd_grid_supported_t dlpd_grid_supported_fn; dlpd_rotate_trilinear_t dlpd_rotate_trilinear_fn;
   dlpd_topk_workspace_bytes_t dlpd_topk_workspace_bytes_fn; dlpd_topk_select_t dlpd_topk_select_fn;
   dlpd_rfft3d_padded_t dlpd_rfft3d_padded_fn; dlpd_zfft_t dlpd_zfft_fn; dlpd_xy_correlate_t dlpd_xy_correlate_fn;
-  dlpd_zifft_real_t dlpd_zifft_real_fn;
+  dlpd_zifft_real_t dlpd_zifft_real_fn; dlpd_hidden_pad_t dlpd_hidden_pad_fn; dlpd_score_rotations_t dlpd_score_rotations_fn;
   SYM(dlpd_version) SYM(dlpd_grid_supported) SYM(dlpd_rotate_trilinear) SYM(dlpd_topk_workspace_bytes) SYM(dlpd_topk_select)
   SYM(dlpd_rfft3d_padded) SYM(dlpd_zfft) SYM(dlpd_xy_correlate) SYM(dlpd_zifft_real)
+  SYM(dlpd_hidden_pad) SYM(dlpd_score_rotations)
   if (dlpd_version_fn() < 100 || dlpd_grid_supported_fn(32) != 1 || dlpd_grid_supported_fn(33) != 0) { fprintf(stderr, "version / grid query\n"); return 1; }
 
   enum { L = 32, N = 64, NZ = 33 };
@@ -128,8 +135,33 @@ int main(int argc, char** argv) {
     if (e > worst) worst = e;
   }
   if (worst > 1e-5) { fprintf(stderr, "correlation with a one-voxel volume is off by %g\n", worst); return 1; }
+
+  /* 4. the one-call driver: identity rotation, the one-voxel ligand, C = 1, no clash, no clip, probe filter -> V[t] = v1[t + (1,2,3)] */
+  const int HP = dlpd_hidden_pad_fn(2);
+  if (HP < 2 || HP > 64) { fprintf(stderr, "dlpd_hidden_pad(2) = %d\n", HP); return 1; }
+  float hw1[64] = {0}, hw2[64] = {0}, hb1[64] = {0};
+  hw1[0] = 1.0f; hw1[1] = -1.0f; hw2[0] = 1.0f; hw2[1] = -1.0f;
+  float *W1t = (float*)dev_alloc((size_t)HP * 4), *b1 = (float*)dev_alloc((size_t)HP * 4), *W2 = (float*)dev_alloc((size_t)HP * 4);
+  to_dev(W1t, hw1, (size_t)HP * 4); to_dev(b1, hb1, (size_t)HP * 4); to_dev(W2, hw2, (size_t)HP * 4);
+  float* Vs = (float*)dev_alloc(N3 * 4);
+  rc = dlpd_score_rotations_fn(v2, spec, R, 1, 1, 0, L, L / 2.0f, W1t, b1, W2, 0.0f, HP, 0, 0.0f, 0.0f, wsA, wsB, Vs, NULL);
+  if (rc != DLPD_OK) { fprintf(stderr, "dlpd_score_rotations failed (%d)\n", rc); return 1; }
+  to_host(hc, Vs, N3 * 4);
+  double worst_driver = 0.0;
+  for (int tx = -L; tx < L; tx++) for (int ty = -L; ty < L; ty++) for (int tz = -L; tz < L; tz++) {
+    const int x = tx + 1, y = ty + 2, z = tz + 3;
+    const float want = (x >= 0 && x < L && y >= 0 && y < L && z >= 0 && z < L) ? h[((size_t)x * L + y) * L + z] : 0.0f;
+    const float got = hc[(((size_t)((tx + N) % N)) * N + (size_t)((ty + N) % N)) * N + (size_t)((tz + N) % N)];
+    const double e = fabs((double)got - (double)want);
+    if (!(e <= worst_driver)) worst_driver = e;
+  }
+  if (!(worst_driver <= 1e-5)) { fprintf(stderr, "dlpd_score_rotations with a one-voxel ligand is off by %g\n", worst_driver); return 1; }
+  if (dlpd_score_rotations_fn(NULL, spec, R, 1, 1, 0, L, L / 2.0f, W1t, b1, W2, 0.0f, HP, 0, 0.0f, 0.0f, wsA, wsB, Vs, NULL) != DLPD_ERR_ARG) {
+    fprintf(stderr, "dlpd_score_rotations: null ligand not refused\n"); return 1;
+  }
+  dev_free(W1t); dev_free(b1); dev_free(W2); dev_free(Vs);
   dev_free(vol); dev_free(out); dev_free(R); dev_free(V); dev_free(sc); dev_free(ix); dev_free(ws); dev_free(v2); dev_free(wsA);
   dev_free(spec); dev_free(wsB); dev_free(corr);
-  printf("c-abi client ok (%s, version %d, correlation error %.2g)\n", argv[2], dlpd_version_fn(), worst);
+  printf("c-abi client ok (%s, version %d, correlation error %.2g, driver error %.2g)\n", argv[2], dlpd_version_fn(), worst, worst_driver);
   return 0;
 }
