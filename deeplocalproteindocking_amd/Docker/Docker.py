@@ -538,6 +538,91 @@ class Docker:
             self.log.write("\n".join(rows) + "\n")
         self.log.flush()
 
+    # ------------------------------------------------------------------ pose clustering (csrc/dlpd_cluster.h; build-defined)
+    def _pose_arrays(self, poses):
+        """Entries of either list form -> (R (K, 3, 3) float64, t (K, 3) float64 in voxels, the entries' own translations,
+        scores): ``top_list`` entries (rot, x, y, z, score) through ``signed_translation``, ``refined_list`` entries
+        (R, (tx, ty, tz), score, src) as they stand (fractions of a voxel included)."""
+        R, t, own, score = [], [], [], []
+        for e in poses:
+            if len(e) == 5:
+                R.append(self.rot.R[int(e[0])].detach().cpu().to(torch.float64).numpy())
+                own.append(self.signed_translation(e[1], e[2], e[3]))
+                score.append(float(e[4]))
+            else:
+                R.append(np.array(e[0], dtype=np.float64).reshape(3, 3))
+                own.append(tuple(e[1]))
+                score.append(float(e[2]))
+            t.append([float(v) for v in own[-1]])
+        return np.stack(R), np.array(t, dtype=np.float64).reshape(-1, 3), own, score
+
+    def cluster(self, ligand_coords, poses=None, radius=None, keep=None, weights=None, rank="score"):
+        """Greedy clustering of a list of poses by the RMSD between them (default: ``self.top_list``; a ``refined_list`` is
+        taken too; neither is touched).  ``ligand_coords`` (n, 3): the ligand's atoms in Angstrom, centred on the origin as
+        the search holds them (``PreparedPair.ligand_atoms``); pose p carries atom x to R_p x + t_p, t_p the entry's
+        translation times ``resolution``; ``weights`` (n) >= 0 select or weigh atoms (C-alpha only, a fixed subset).  In list
+        order (best score first) a pose is a centre iff no earlier centre lies within ``radius`` Angstrom of it (required:
+        there is no default), every other pose joins the first such centre.  ``keep``: at most that many clusters.
+        ``rank="size"`` re-sorts the clusters by population (stable: equal sizes keep their score order) before ``keep``
+        cuts.  The list is clustered in the search frame -- a rigid motion common to all poses changes no distance -- and
+        ``randomize_rot`` is undone by the writer alone.
+        -> ``self.clustered_list``: entries (R float64 (3, 3), the centre's translation in voxels, score, position of the centre
+        in ``poses``, size of the cluster), and ``self.cluster_labels`` (len(poses)) int32: the entry of ``clustered_list``
+        each pose belongs to, -1 for a pose none of the kept clusters covers.  At most 65,536 poses.
+        Every rank clusters the same (gathered) list; there is no collective here."""
+        from deeplocalproteindocking_amd import ops
+        if radius is None or not float(radius) >= 0.0:
+            raise Exception("cluster needs a radius in Angstrom (>= 0); there is no default", radius)
+        if rank not in ("score", "size"):
+            raise Exception("Unknown cluster ranking", rank)
+        if keep is not None and int(keep) <= 0:
+            raise Exception("cluster keep must be positive", keep)
+        poses = list(self.top_list if poses is None else poses)
+        self.clustered_list, self.cluster_labels = [], np.zeros(0, dtype=np.int32)
+        if not poses:
+            return self.clustered_list
+        R, t, own, score = self._pose_arrays(poses)
+        coords = ligand_coords.detach().cpu().numpy() if torch.is_tensor(ligand_coords) else np.asarray(ligand_coords)
+        E, _ = ops.pose_embedding(coords.reshape(-1, 3), R, t * float(self.resolution), weights, device=self.device)
+        first = None if rank == "size" or keep is None else int(keep)
+        centres, sizes, labels = ops.pose_cluster(E, float(radius), max_clusters=first, lib=self._lib)
+        centres, sizes, labels = centres.cpu().numpy(), sizes.cpu().numpy(), labels.cpu().numpy()
+        order = np.arange(len(centres))
+        if rank == "size":
+            order = np.argsort(-sizes.astype(np.int64), kind="stable")
+            if keep is not None:
+                order = order[:int(keep)]
+            place = np.full(len(centres) + 1, -1, dtype=np.int32)          # (the last slot: label -1 stays -1)
+            place[order] = np.arange(len(order), dtype=np.int32)
+            labels = place[labels]
+        self.clustered_list = [(R[c].copy(), own[c], score[c], int(c), int(sizes[n])) for n, c in ((n, int(centres[n])) for n in order)]
+        self.cluster_labels = labels.astype(np.int32)
+        return self.clustered_list
+
+    def cluster_prepared(self, prepared, poses=None, radius=None, keep=None, weights=None, rank="score"):
+        """``cluster`` with the ligand's atoms taken from the ``PreparedPair`` the search ran on (origin-centred, on the device)."""
+        lc, ln, _ = prepared.ligand_atoms
+        n = int(ln.sum())
+        return self.cluster(lc.reshape(-1)[:3 * n].reshape(n, 3), poses=poses, radius=radius, keep=keep, weights=weights, rank=rank)
+
+    def write_clustered_conformations(self):
+        """The centres of ``self.clustered_list`` in the format of ``write_conformations`` (13 tab-separated ``%f`` columns,
+        ``randomize_rot`` undone the same way): Results.DockerParser reads it unchanged."""
+        if self.log is None:
+            return
+        undo = self.randR.squeeze().t().to(torch.double) if self.randomize_rot else None
+        rows = []
+        for R, tt, score, _, _ in getattr(self, "clustered_list", []):
+            r = torch.as_tensor(R, dtype=torch.double)
+            t = torch.tensor(tt, dtype=torch.double) * self.resolution
+            if undo is not None:
+                t, r = undo @ t, undo @ r
+            cols = [float(v) for v in r.reshape(-1)] + [float(v) for v in t] + [score]
+            rows.append("\t".join("%f" % v for v in cols))
+        if rows:
+            self.log.write("\n".join(rows) + "\n")
+        self.log.flush()
+
     def refine_prepared(self, prepared, perturbations=None, radius=1, poses=None):
         """``refine`` for a target given as files: the ``PreparedPair`` the SE3 search ran on (``prepare`` / ``dockSE3``) holds
         the volumes; the clash channel is re-projected from the rotated ligand atoms as ``dockSE3`` does (Docker.py:221-224)."""

@@ -567,3 +567,6 @@ int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int*
 }
 
 }  // extern "C"
+
+// pose clustering of the finished list (build-defined): pairwise rigid-pose RMSD, neighbour bitmap, greedy scan
+#include "dlpd_cluster.h"

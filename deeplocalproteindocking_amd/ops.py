@@ -1027,3 +1027,99 @@ class MultiplyVolumes(nn.Module):
             raise RuntimeError("dlpd: MultiplyVolumes expects (B, C, L, L, L) pairs and T (B, 3)")
         Ti = torch.as_tensor(T).detach().trunc().to(torch.int32).to(rec.device)
         return local_correlate(rec, lig, Ti, radius=0, scale=1, coarse="trunc", lib=self.lib).reshape(rec.shape[0], rec.shape[1])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Pose clustering (csrc/dlpd_cluster.h; build-defined, the reference has no counterpart)
+# ----------------------------------------------------------------------------------------------------------------------
+POSE_CLUSTER_MAX = 65536
+
+
+def pose_embedding(coords, R, t, weights=None, device=None):
+    """Rigid poses of ONE ligand as points whose Euclidean distance is the pose RMSD: ``coords`` (n, 3) in Angstrom (centred on
+    the origin: the frame the poses ``x -> R x + t`` act in), ``R`` (K, 3, 3), ``t`` (K, 3) in Angstrom, ``weights`` (n) >= 0
+    (normalised here to sum 1; None: every atom alike).  With c = sum w x, S = sum w (x - c)(x - c)^T = V L V^T and
+    B = V L^(1/2), e_p = (R_p c + t_p, vec(R_p B)) and
+        sum_k w_k |(R_i x_k + t_i) - (R_j x_k + t_j)|^2 = |e_i - e_j|^2:
+    a translation part and a rotation part, both non-negative (no cancellation between them).  Computed in float64 on the
+    host -> (E (K, 12) float32 on ``device`` (default: where ``coords`` lives), M = max|e| -- what the float32 error of a
+    distance scales with)."""
+    import numpy as np
+
+    def host(a):
+        return (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)
+    if device is None:
+        device = coords.device if torch.is_tensor(coords) else "cpu"
+    x, Rm, tt = host(coords).reshape(-1, 3), host(R).reshape(-1, 3, 3), host(t).reshape(-1, 3)
+    if x.shape[0] == 0 or Rm.shape[0] != tt.shape[0]:
+        raise RuntimeError("dlpd: pose_embedding expects coords (n, 3), R (K, 3, 3) and t (K, 3)")
+    if weights is None:
+        w = np.full(x.shape[0], 1.0 / x.shape[0])
+    else:
+        w = host(weights).reshape(-1)
+        if w.shape[0] != x.shape[0] or (w < 0).any() or not w.sum() > 0:
+            raise RuntimeError("dlpd: pose_embedding weights must be (n) non-negative numbers with a positive sum")
+        w = w / w.sum()
+    c = (w[:, None] * x).sum(axis=0)
+    y = x - c
+    lam, V = np.linalg.eigh((w[:, None, None] * y[:, :, None] * y[:, None, :]).sum(axis=0))
+    B = V * np.sqrt(np.clip(lam, 0.0, None))[None, :]
+    E = np.concatenate([Rm @ c + tt, (Rm @ B).reshape(-1, 9)], axis=1)
+    M = float(np.abs(E).max()) if E.size else 0.0
+    return torch.from_numpy(E.astype(np.float32)).to(device), M
+
+
+def _embedded(E, name, lib):
+    E = _check(E, name, lib)
+    if E.dim() != 2 or E.shape[1] != 12 or E.shape[0] == 0:
+        raise RuntimeError("dlpd: %s must be (K, 12) embedded poses (ops.pose_embedding), K > 0" % name)
+    return E
+
+
+def pose_rmsd(Ea, Eb=None, lib=None):
+    """(Ka, Kb) float32: the RMSD between every pose of ``Ea`` and every pose of ``Eb`` (default: ``Ea`` itself -- then
+    symmetric bit for bit, with an exact zero wherever two poses are equal)."""
+    lib_ = lib or get_lib()
+    Ea = _embedded(Ea, "Ea", lib)
+    Eb = Ea if Eb is None else _embedded(Eb, "Eb", lib)
+    D = torch.empty(Ea.shape[0], Eb.shape[0], dtype=torch.float32, device=Ea.device)
+    lib_.call("dlpd_pose_rmsd", _ptr(Ea), _ptr(Eb), _ptr(D), Ea.shape[0], Eb.shape[0], _stream(Ea.device))
+    return D
+
+
+def pose_within(E, radius, lib=None):
+    """The neighbour bitmap alone: (K, ceil(K / 64)) int64 words, bit (j & 63) of word [i, j >> 6] set iff pose j lies
+    within ``radius`` of pose i.  For analysis and the tests: it is K^2 / 8 bytes, and ``pose_cluster`` never shows it."""
+    lib_ = lib or get_lib()
+    E = _embedded(E, "E", lib)
+    K = E.shape[0]
+    mask = torch.empty(K, (K + 63) // 64, dtype=torch.int64, device=E.device)
+    lib_.call("dlpd_pose_within", _ptr(E), K, float(radius), _ptr(mask), _stream(E.device))
+    return mask
+
+
+def pose_cluster(E, radius, max_clusters=None, lib=None):
+    """Greedy clustering of a list of embedded poses in ITS order (best first): pose i is a centre iff no earlier centre lies
+    within ``radius`` (d <= radius) of it, every other pose joins the first centre within ``radius``; after ``max_clusters``
+    centres the scan stops and what they do not cover is labelled -1.  -> (centres (n) list positions, sizes (n), the centre
+    included, labels (K) index into centres) int32 on E's device.  The K x K bitmap lives in a workspace on the device
+    (K^2 / 8 bytes: 512 MB at K = 65,536, the limit) and is never copied to the host."""
+    lib_ = lib or get_lib()
+    E = _embedded(E, "E", lib)
+    K, dev = E.shape[0], E.device
+    if K > POSE_CLUSTER_MAX:
+        raise RuntimeError("dlpd: pose_cluster takes at most %d poses, got %d" % (POSE_CLUSTER_MAX, K))
+    m = K if max_clusters is None else int(max_clusters)
+    if m <= 0:
+        raise RuntimeError("dlpd: pose_cluster max_clusters must be positive")
+    m = min(m, K)
+    nbytes = lib_.call("dlpd_pose_cluster_ws", K)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    centres = torch.empty(m, dtype=torch.int32, device=dev)
+    sizes = torch.empty(m, dtype=torch.int32, device=dev)
+    labels = torch.empty(K, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib_.call("dlpd_pose_cluster", _ptr(E), K, float(radius), m, _ptr(centres), _ptr(sizes), _ptr(labels), _ptr(count), _ptr(ws),
+              nbytes, _stream(dev))
+    n = int(count.item())
+    return centres[:n], sizes[:n], labels

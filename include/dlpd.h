@@ -532,6 +532,28 @@ int dlpd_topk_merge(const float* cand_score, const int* cand_idx, const int* rot
 int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int* rot_ids, int nb, int K,
                         void* glist, void* tau_out, void* stream);
 
+/* Pose clustering of a finished list.  BUILD-DEFINED, all four entries: the reference has no counterpart and no call site
+ * (Docker.cluster is this build's own step after the search).  A rigid pose p = (R_p, t_p) of one ligand is handed over as
+ * its embedding e_p, 12 floats (ops.pose_embedding): the RMSD between two poses over the ligand's (weighted) atoms is the
+ * Euclidean distance of their embeddings.  Every squared distance is one fma chain over the twelve differences in a fixed
+ * order, so d(i, j) and d(j, i) have the same bits and equal poses give exactly 0.  K, Ka, Kb <= 65536 (else
+ * DLPD_ERR_UNSUPPORTED); K <= 0, a null pointer, a negative or NaN radius, a short workspace: DLPD_ERR_ARG; on an error
+ * nothing is launched and nothing is written.
+ * dlpd_pose_rmsd: D (Ka, Kb) = d(Ea[i], Eb[j]).
+ * dlpd_pose_within: the neighbour bitmap alone -- mask holds K rows of W = ceil(K / 64) 64-bit words, row-major: bit (j & 63)
+ *   of mask[i * W + (j >> 6)] is set iff d(i, j)^2 <= radius^2 in float32; bits of columns >= K are zero.
+ * dlpd_pose_cluster: the greedy clustering of the list in its own order (best first).  Pose i is a centre iff no earlier
+ *   centre lies within radius of it; every other pose belongs to the first centre within radius.  The scan stops after
+ *   max_clusters centres (<= 0 or > K: no limit); a pose none of them covers gets label -1.  centres / sizes: the first *count
+ *   entries are written (room for min(K, max_clusters)); labels (K); count (1); all int32 on the device.  ws: the bitmap,
+ *   dlpd_pose_cluster_ws(K) = K * ceil(K / 64) * 8 bytes (0 for an unsupported K), 8-byte aligned; it never leaves the
+ *   device.  Integer work once the bitmap stands: the same input gives the same bytes. */
+int dlpd_pose_rmsd(const float* Ea, const float* Eb, float* D, int Ka, int Kb, void* stream);
+int dlpd_pose_within(const float* E, int K, float radius, void* mask, void* stream);
+size_t dlpd_pose_cluster_ws(int K);
+int dlpd_pose_cluster(const float* E, int K, float radius, int max_clusters, int* centres, int* sizes, int* labels, int* count,
+                      void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,10 @@ without the benchmark table: representation -> exhaustive rotation x translation
                                            # trials per pose (Docker.minimize) -> <out>.minimized.dat beside the .dat
         [--minimize-translation]           # with --minimize: a rigid-body descent, the translation moves by fractions of a voxel
                                            # too (Docker.minimize(translation=True)); the .dat carries T + s times the resolution
+        [--cluster RADIUS[:KEEP]]          # SE3: cluster the LAST list the run produced (the top list, or the refined / minimised
+                                           # one) by pose RMSD over the ligand's atoms, greedily in score order, RADIUS in Angstrom,
+                                           # at most KEEP clusters (Docker.cluster) -> <out>.clustered.dat (the centres) and
+                                           # <out>.clustered.sizes.txt (their populations, one per line) beside the .dat
 
 Multi-GPU: launch with torch.distributed.run; rotations are sharded over the ranks, rank 0 writes."""
 import argparse
@@ -21,6 +25,30 @@ sys.path.insert(0, ROOT)
 import torch
 
 import __graft_entry__ as entry
+
+
+def parse_cluster(spec):
+    """RADIUS[:KEEP] -> (radius in Angstrom, keep or None)"""
+    part = spec.split(":")
+    return float(part[0]), (int(part[1]) if len(part) > 1 and part[1] else None)
+
+
+def cluster_and_write(docker, prepared, out, radius, keep=None, poses=None, rank=0):
+    """The --cluster step: ``Docker.cluster_prepared`` on ``poses`` (None: the top list), then <out>.clustered.dat and
+    <out>.clustered.sizes.txt written by ``rank`` 0 (every rank clusters the same gathered list)."""
+    docker.cluster_prepared(prepared, poses=poses, radius=radius, keep=keep)
+    stem = (out[:-4] if out.endswith(".dat") else out) + ".clustered"
+    name, sizes_name = stem + ".dat", stem + ".sizes.txt"
+    if rank == 0:
+        docker.new_log(name, rewrite=True)
+        docker.write_clustered_conformations()
+        docker.cleanup()
+        with open(sizes_name, "w") as f:
+            f.write("".join("%d\n" % e[4] for e in docker.clustered_list))
+        sizes = [e[4] for e in docker.clustered_list]
+        print("wrote", name, "(%d clusters of %d poses, largest %d, best score %f)" %
+              (len(sizes), sum(sizes), max(sizes) if sizes else 0, docker.clustered_list[0][2] if sizes else float("nan")))
+    return name, sizes_name
 
 
 def main():
@@ -41,6 +69,7 @@ def main():
     ap.add_argument("--refine", default=None, metavar="ANGLE[:STEPS[:RADIUS]]")
     ap.add_argument("--minimize", default=None, type=int, metavar="STEPS")
     ap.add_argument("--minimize-translation", action="store_true")
+    ap.add_argument("--cluster", default=None, metavar="RADIUS[:KEEP]")
     args = ap.parse_args()
     entry.build()
     from deeplocalproteindocking_amd.Docker import Docker
@@ -73,8 +102,10 @@ def main():
         ap.error("--minimize-translation needs --minimize STEPS")
     if args.minimize is not None and args.group != "SE3":
         ap.error("--minimize needs -group SE3 (the ligand's volumes are rotated, not re-represented)")
+    if args.cluster is not None and args.group != "SE3":
+        ap.error("--cluster needs -group SE3 (the poses move the prepared ligand's atoms)")
     with torch.no_grad():
-        prepared = docker.prepare(args.receptor, args.ligand, "SE3") if (refine or args.minimize is not None) else None
+        prepared = docker.prepare(args.receptor, args.ligand, "SE3") if (refine or args.minimize is not None or args.cluster is not None) else None
         (docker.dockSE3 if args.group == "SE3" else docker.dockE3)(args.receptor, args.ligand, args.batch_size, prepared=prepared)
     docker.cleanup()
     if rank == 0:
@@ -96,6 +127,10 @@ def main():
             docker.write_refined_conformations()
             docker.cleanup()
             print("wrote", name, "(%d poses, best score %f)" % (len(docker.refined_list), docker.refined_list[0][2]))
+    if args.cluster is not None:
+        radius, keep = parse_cluster(args.cluster)
+        last = docker.refined_list if (refine or args.minimize is not None) else None       # (None: the top list)
+        cluster_and_write(docker, prepared, args.out, radius, keep, poses=last, rank=rank)
     if world > 1:
         dist.destroy_process_group()
 
