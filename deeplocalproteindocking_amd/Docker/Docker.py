@@ -623,6 +623,53 @@ class Docker:
             self.log.write("\n".join(rows) + "\n")
         self.log.flush()
 
+    # ------------------------------------------------------------------ evaluation against a native (csrc/dlpd_evaluate.h)
+    def dat_frame_poses(self, poses):
+        """Entries of ``top_list``, ``refined_list`` or ``clustered_list`` -> (K, 12) float64, R row-major then t in Angstrom, in
+        the frame of the .dat file: what ``write_conformations`` / ``write_refined_conformations`` /
+        ``write_clustered_conformations`` put on a line before ``%f`` rounds it (``randomize_rot`` undone by randR^T on both R
+        and t).  A ``clustered_list`` entry has five fields as a ``top_list`` entry has: the forms are told apart by the first
+        field, a rotation index or a matrix."""
+        undo = self.randR.squeeze().t().to(torch.double).numpy() if self.randomize_rot else None
+        out = np.zeros((len(poses), 12), dtype=np.float64)
+        for k, e in enumerate(poses):
+            if np.ndim(e[0]) == 0:
+                r = self.rot.R[int(e[0])].detach().cpu().to(torch.float64).numpy()
+                t = np.array(self.signed_translation(e[1], e[2], e[3]), dtype=np.float64)
+            else:
+                r = np.array(e[0], dtype=np.float64).reshape(3, 3)
+                t = np.array([float(v) for v in e[1]], dtype=np.float64)
+            t = t * float(self.resolution)
+            if undo is not None:
+                t, r = undo @ t, undo @ r
+            out[k, :9], out[k, 9:] = r.reshape(-1), t
+        return out
+
+    def evaluate(self, native, poses=None):
+        """How good every pose of a list is (default: ``self.top_list``; ``refined_list`` and ``clustered_list`` entries are
+        taken too; none of the lists is touched): ``native`` is a ``Results.InterfaceSelection.NativeReference`` of the target
+        (``native_reference`` of the bound and unbound files).  -> ``self.evaluation``, a dict of numpy arrays aligned with
+        the poses: ``irmsd`` and ``lrmsd`` in Angstrom, ``fnat`` (float64) and ``capri`` (int32, 0 incorrect .. 3 high).
+        At most 65,536 poses.  Every rank evaluates the same (gathered) list; there is no collective here."""
+        from deeplocalproteindocking_amd import ops
+        poses = list(self.top_list if poses is None else poses)
+        self.evaluation = {"irmsd": np.zeros(0), "lrmsd": np.zeros(0), "fnat": np.zeros(0), "capri": np.zeros(0, dtype=np.int32)}
+        if not poses:
+            return self.evaluation
+        got = ops.pose_evaluate(self.dat_frame_poses(poses), native.to(self.device), lib=self._lib)
+        self.evaluation = {k: v.cpu().numpy() for k, v in zip(("irmsd", "lrmsd", "fnat", "capri"), got)}
+        return self.evaluation
+
+    def write_evaluation(self):
+        """``self.evaluation`` into the open log, one line per pose: irmsd, lrmsd, fnat (``%f``) and the class, tab-separated"""
+        if self.log is None:
+            return
+        ev = getattr(self, "evaluation", None)
+        if ev is not None and len(ev["capri"]):
+            self.log.write("\n".join("%f\t%f\t%f\t%d" % (i, l, f, c) for i, l, f, c in
+                                     zip(ev["irmsd"], ev["lrmsd"], ev["fnat"], ev["capri"])) + "\n")
+        self.log.flush()
+
     def refine_prepared(self, prepared, perturbations=None, radius=1, poses=None):
         """``refine`` for a target given as files: the ``PreparedPair`` the SE3 search ran on (``prepare`` / ``dockSE3``) holds
         the volumes; the clash channel is re-projected from the rotated ligand atoms as ``dockSE3`` does (Docker.py:221-224)."""

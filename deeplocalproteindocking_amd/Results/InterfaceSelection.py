@@ -210,3 +210,170 @@ def evaluate_target(parser, target_name, bound_receptor_pdb, bound_ligand_pdb, u
     n = len(parser.target_dict["conformations"])
     n = n if num_conf is None else min(n, int(num_conf))
     return [parser.interface_rmsd(mobile, static, i) for i in range(n)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Evaluation on the device (csrc/dlpd_evaluate.h): I-RMSD, L-RMSD, fraction of native contacts, CAPRI class
+# ----------------------------------------------------------------------------------------------------------------------
+
+def _residue(s, i):
+    return (str(s["chain"][i]), int(s["resnum"][i]), THREE_TO_ONE[str(s["resname"][i])])
+
+
+def native_contact_pairs(receptor, ligand, contact_dist=5.0):
+    """The native contacts of a (bound) complex: the residue pairs with any atom pair within ``contact_dist`` -- the
+    ``contacts`` set of processing_utils.py:183-216 -- under the filters of ``get_contacts`` (standard amino acids, no
+    insertion code) -> sorted list of ((chain, resnum, name) of the receptor, (chain, resnum, name) of the ligand)."""
+    from scipy.spatial import cKDTree
+    ir, il = np.nonzero(_standard(receptor))[0], np.nonzero(_standard(ligand))[0]
+    if not len(ir) or not len(il):
+        return []
+    hits = cKDTree(ligand["xyz"][il]).query_ball_tree(cKDTree(receptor["xyz"][ir]), contact_dist)
+    pairs = set()
+    for a, hs in enumerate(hits):
+        for h in hs:
+            pairs.add((_residue(receptor, ir[h]), _residue(ligand, il[a])))
+    return sorted(pairs)
+
+
+def transfer_pairs(pairs, bound_receptor, unbound_receptor, receptor_match, bound_ligand, unbound_ligand, ligand_match):
+    """Residue pairs of the bound complex as residue pairs of the unbound structures, each residue through
+    ``transfer_selection``; a pair with an unaligned residue is dropped -> (kept bound pairs, unbound pairs), entry by entry."""
+    def table(residues, src, dst, match):
+        out = {}
+        for res in sorted(set(residues)):
+            kept, moved = transfer_selection([res], src, dst, match)
+            out[res] = moved[0] if kept else None
+        return out
+    rec = table([p[0] for p in pairs], bound_receptor, unbound_receptor, receptor_match)
+    lig = table([p[1] for p in pairs], bound_ligand, unbound_ligand, ligand_match)
+    kept = [p for p in pairs if rec[p[0]] is not None and lig[p[1]] is not None]
+    return kept, [(rec[p[0]], lig[p[1]]) for p in kept]
+
+
+def aligned_ca(bound, unbound, match):
+    """C-alpha coordinates of every aligned residue pair that has one in both structures -> (bound (m, 3), unbound (m, 3))"""
+    sb, su = chain_sequences(bound), chain_sequences(unbound)
+    pb, pu = [], []
+    for ch, (other, _, alignment) in match.items():
+        for i in sorted(alignment):
+            p, q = _ca_of(bound, ch, sb[ch][1][i]), _ca_of(unbound, other, su[other][1][alignment[i]])
+            if p is not None and q is not None:
+                pb.append(p)
+                pu.append(q)
+    return np.asarray(pb, dtype=np.float64).reshape(-1, 3), np.asarray(pu, dtype=np.float64).reshape(-1, 3)
+
+
+def kabsch_fit(mobile, static):
+    """The rigid motion x -> Q x + s that carries ``mobile`` (n, 3) onto ``static`` (n, 3) with the least RMSD (float64 SVD)"""
+    cm, cs = mobile.mean(axis=0), static.mean(axis=0)
+    U, _, Vt = np.linalg.svd((mobile - cm).T @ (static - cs))
+    d = np.sign(np.linalg.det(Vt.T @ U.T))
+    Q = Vt.T @ np.diag([1.0, 1.0, d if d != 0 else 1.0]) @ U.T
+    return Q, cs - Q @ cm
+
+
+def _residue_atoms(s, residue, shift):
+    sel = (s["chain"] == residue[0]) & (s["resnum"] == residue[1]) & (s["icode"] == " ")
+    return s["xyz"][sel] + shift
+
+
+def _packed_atoms(s, residues, shift):
+    """all ATOM records of the residues, residue after residue -> (atoms (n, 3) float64, {residue: (first, end)})"""
+    rows, where, n = [], {}, 0
+    for res in residues:
+        xyz = _residue_atoms(s, res, shift)
+        where[res] = (n, n + len(xyz))
+        rows.append(xyz)
+        n += len(xyz)
+    return (np.concatenate(rows) if rows else np.zeros((0, 3))), where
+
+
+class NativeReference(object):
+    """What the evaluation kernels need of one target, and the host-side pieces it was built from.
+    For the kernels: ``moments`` (nI + 1, 48) float64 and ``counts`` (host) -- ops.native_moments; ``rec_atoms`` / ``lig_atoms``
+    float32, the interface atoms of the unbound structures in the docking frame / the ligand's own frame, residue-contiguous;
+    ``ranges`` (C, 4) int32 with its host copy ``ranges_host``; ``C``; ``contact_dist``.  On the host: ``interfaces`` (the
+    selections of ``unbound_interfaces``), ``pairs`` (the interface point sets), ``ligand_ca`` / ``target_ca`` (the points of the
+    ligand RMSD), ``superposition`` (Q, s: bound frame -> docking frame), ``contacts`` (the transferred residue pairs) and
+    ``rec_atoms64`` / ``lig_atoms64``.  ``to(device)`` moves the first group."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+        self.device = torch.device("cpu")
+        self.moments = torch.from_numpy(self.moments_host)
+        self.rec_atoms = torch.from_numpy(self.rec_atoms64.astype(np.float32))
+        self.lig_atoms = torch.from_numpy(self.lig_atoms64.astype(np.float32))
+        self.ranges = torch.from_numpy(self.ranges_host)
+
+    def to(self, device):
+        for name in ("moments", "rec_atoms", "lig_atoms", "ranges"):
+            setattr(self, name, getattr(self, name).to(device))
+        self.device = self.moments.device
+        return self
+
+
+def native_reference_from_points(pairs, ligand_ca, target_ca, rec_atoms, lig_atoms, ranges, contact_dist=5.0, **host):
+    """A ``NativeReference`` from explicit point sets (``native_reference`` without the PDB files): the arguments of
+    ops.native_moments, the two interface atom arrays (float64, residue-contiguous) and the contacts' atom ranges (C, 4)."""
+    from deeplocalproteindocking_amd import ops
+    moments, counts = ops.native_moments(pairs, ligand_ca, target_ca)
+    ranges = np.ascontiguousarray(np.asarray(ranges, dtype=np.int32).reshape(-1, 4))
+    return NativeReference(moments_host=moments, counts=counts, rec_atoms64=np.asarray(rec_atoms, dtype=np.float64).reshape(-1, 3),
+                           lig_atoms64=np.asarray(lig_atoms, dtype=np.float64).reshape(-1, 3), ranges_host=ranges, C=int(ranges.shape[0]),
+                           contact_dist=float(contact_dist), pairs=pairs, ligand_ca=ligand_ca, target_ca=target_ca, **host)
+
+
+def native_reference(bound_receptor, bound_ligand, unbound_receptor, unbound_ligand, contact_dist=5.0):
+    """Everything the evaluation of one target's poses needs (structures as ``read_structure`` gives them, or file names).
+    The docking frame: each unbound structure about its own bounding-box centre, the ligand then placed by the pose.
+      I-RMSD   the interface pairs of ``unbound_interfaces``, C-alpha, as ``evaluate_target`` selects them;
+      L-RMSD   every aligned ligand residue with a C-alpha in both structures; the bound ligand's are carried into the docking
+               frame by the Kabsch fit of the bound receptor's aligned C-alphas onto the unbound receptor's;
+      fnat     ``native_contact_pairs`` of the bound complex, transferred (``transfer_pairs``); per contact all ATOM records of
+               the two unbound residues."""
+    br, bl, ur, ul = (read_structure(s) if isinstance(s, str) else s for s in (bound_receptor, bound_ligand, unbound_receptor, unbound_ligand))
+    shift_r, shift_l = -bbox_centre(ur), -bbox_centre(ul)
+    interfaces = unbound_interfaces(br, bl, ur, ul, contact_dist)
+    pairs = []
+    for urec_sel, ulig_sel, brec_sel, blig_sel in interfaces:
+        pairs.append((select_ca(ur, urec_sel, shift_r).numpy(), select_ca(ul, ulig_sel, shift_l).numpy(),
+                      torch.cat([select_ca(br, brec_sel), select_ca(bl, blig_sel)], dim=0).numpy()))
+    rec_match, lig_match = best_chain_match(br, ur), best_chain_match(bl, ul)
+    b_ca, u_ca = aligned_ca(br, ur, rec_match)
+    if len(b_ca) < 3:
+        raise Exception("Too few aligned receptor residues for a superposition", len(b_ca))
+    Q, s = kabsch_fit(b_ca, u_ca + shift_r)
+    bl_ca, ul_ca = aligned_ca(bl, ul, lig_match)
+    if len(bl_ca) < 1:
+        raise Exception("No aligned ligand residue")
+    ligand_ca, target_ca = ul_ca + shift_l, bl_ca @ Q.T + s
+    bound_pairs, contacts = transfer_pairs(native_contact_pairs(br, bl, contact_dist), br, ur, rec_match, bl, ul, lig_match)
+    rec_atoms, rec_at = _packed_atoms(ur, sorted(set(c[0] for c in contacts)), shift_r)
+    lig_atoms, lig_at = _packed_atoms(ul, sorted(set(c[1] for c in contacts)), shift_l)
+    ranges = [rec_at[r] + lig_at[l] for r, l in contacts]
+    return native_reference_from_points(pairs, ligand_ca, target_ca, rec_atoms, lig_atoms, ranges, contact_dist, interfaces=interfaces,
+                                        superposition=(Q, s), contacts=contacts, bound_contacts=bound_pairs)
+
+
+def conformation_poses(conformations):
+    """``parse_output``'s conformations (truncated translations included) -> (K, 12) float64: R row-major, then t"""
+    return np.stack([np.concatenate([R.numpy().reshape(9), t.numpy().reshape(3)]) for R, t, _ in conformations]).astype(np.float64)
+
+
+def evaluate_target_device(parser, target_name, bound_receptor_pdb, bound_ligand_pdb, unbound_receptor_pdb, unbound_ligand_pdb,
+                           num_conf=None, contact_dist=5.0, device="cuda", lib=None):
+    """``evaluate_target`` on the device and for all four quantities: every conformation of ``<decoys_dir>/<target_name>.dat``
+    (None if the file is missing), poses as ``parse_output`` keeps them, in one call -> dict of numpy arrays ``irmsd``,
+    ``lrmsd``, ``fnat`` (float64) and ``capri`` (int32), plus the ``native`` reference they were measured against."""
+    from deeplocalproteindocking_amd import ops
+    if parser.parse_output(target_name, header_only=False) is None:
+        return None
+    confs = parser.target_dict["conformations"]
+    n = len(confs) if num_conf is None else min(len(confs), int(num_conf))
+    native = native_reference(bound_receptor_pdb, bound_ligand_pdb, unbound_receptor_pdb, unbound_ligand_pdb, contact_dist).to(device)
+    out = {"irmsd": np.zeros(0), "lrmsd": np.zeros(0), "fnat": np.zeros(0), "capri": np.zeros(0, dtype=np.int32), "native": native}
+    if n:
+        got = ops.pose_evaluate(conformation_poses(confs[:n]), native, lib=lib)
+        out.update({k: v.cpu().numpy() for k, v in zip(("irmsd", "lrmsd", "fnat", "capri"), got)})
+    return out

@@ -124,6 +124,9 @@ SIGNATURES = {
     "dlpd_pose_within": (_i, [_p, _i, _f, _p, _p]),
     "dlpd_pose_cluster_ws": (_sz, [_i]),
     "dlpd_pose_cluster": (_i, [_p, _i, _f, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "dlpd_pose_native_rmsd": (_i, [_p, _i, _p, _p, _i, _p, _p, _p]),
+    "dlpd_pose_native_contacts": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _f, _p, _p]),
+    "dlpd_pose_capri": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
 }
 
 ERRORS = {1: "DLPD_ERR_ARG (bad pointer/size)", 2: "DLPD_ERR_UNSUPPORTED (size not compiled)",

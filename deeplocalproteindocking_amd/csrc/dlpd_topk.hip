@@ -570,3 +570,6 @@ int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int*
 
 // pose clustering of the finished list (build-defined): pairwise rigid-pose RMSD, neighbour bitmap, greedy scan
 #include "dlpd_cluster.h"
+
+// evaluation of the finished list against a native complex: I-RMSD, L-RMSD, native contacts, CAPRI class
+#include "dlpd_evaluate.h"

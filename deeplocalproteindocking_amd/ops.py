@@ -1123,3 +1123,182 @@ def pose_cluster(E, radius, max_clusters=None, lib=None):
               nbytes, _stream(dev))
     n = int(count.item())
     return centres[:n], sizes[:n], labels
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Pose evaluation against a native complex (csrc/dlpd_evaluate.h)
+# ----------------------------------------------------------------------------------------------------------------------
+EVAL_REC = 48                     # doubles per record of the moment block
+EVAL_MAX_INTERFACES = 16
+EVAL_MAX_LIGAND_ATOMS = 2048
+
+
+def _fsum_columns(X):
+    import math
+    import numpy as np
+    return np.array([math.fsum(X[:, j]) for j in range(X.shape[1])], dtype=np.float64)
+
+
+def _centred(X):
+    """(n, 3) float64 -> (X about its mean, the mean).  Two passes: the first mean is exact to a rounding of its size, the second
+    removes what that rounding left, so the rows sum to zero to a rounding of a CENTRED coordinate."""
+    import numpy as np
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    if X.shape[0] == 0:
+        return X, np.zeros(3)
+    c1 = _fsum_columns(X) / X.shape[0]
+    X1 = X - c1
+    c2 = _fsum_columns(X1) / X.shape[0]
+    return X1 - c2, c1 + c2
+
+
+def _moment(X, Y):
+    """sum_k X[k, i] Y[k, j] -> (3, 3): every product rounded once, the sum exact (math.fsum) and rounded once"""
+    import math
+    import numpy as np
+    out = np.zeros((3, 3))
+    for i in range(3):
+        for j in range(3):
+            out[i, j] = math.fsum(X[:, i] * Y[:, j])
+    return out
+
+
+def native_moments(pairs, ligand_ca, target_ca):
+    """The moment block of a target for ``pose_native_rmsd``: host float64 packing, no device work.
+    ``pairs``: [(a (nr, 3), y (nl, 3), q (nr + nl, 3))], one entry per interface pair -- the receptor's interface points in the
+    docking frame, the ligand's in ITS frame (a pose carries y to R y + t) and the static points of the native complex,
+    receptor rows first, in any frame (nr >= 0, nl >= 1, at most 16 pairs).  ``ligand_ca`` (m, 3) / ``target_ca`` (m, 3): the
+    points of the ligand RMSD in the ligand's frame and where the native puts them in the docking frame.
+    Every point set is taken about its own centroid (two-pass, so the centred rows sum to zero to a rounding of themselves):
+    a common shift of the mobile set changes no superposed RMSD, and the centroids go into the block so that the kernel adds
+    R cy - ca to a pose's translation.  Sums of products are exact sums (math.fsum) of once-rounded products: the error of a
+    moment does not grow with the number of points.
+    -> (moments (nI + 1, 48) float64: nI interface records  A[9] Y[9] s[3] sa[3] sy[3] Saa Syy Gq ca[3] cy[3] Cyy[6]  with
+    A = sum a q^T, Y = sum y q^T, s = sum_lig q, sa = sum a, sy = sum y, Cyy = sum y y^T (xx xy xz yy yz zz: a pose's matrix
+    need not be a rotation to the last bit, the kernel takes sum |R y|^2 from it), then the ligand record  M[9] sy[3] sz[3] Syy
+    Szz cy[3] cz[3] Cyy[6]  with M = sum z y^T;  counts (nI + 1, 2) int32: (nr, nl) of every record)."""
+    import math
+    import numpy as np
+    pairs = list(pairs)
+    if not 1 <= len(pairs) <= EVAL_MAX_INTERFACES:
+        raise RuntimeError("dlpd: native_moments takes 1 to %d interface pairs, got %d" % (EVAL_MAX_INTERFACES, len(pairs)))
+    nI = len(pairs)
+    mom, counts = np.zeros((nI + 1, EVAL_REC)), np.zeros((nI + 1, 2), dtype=np.int32)
+    for p, (a, y, q) in enumerate(pairs):
+        a, ca = _centred(a)
+        y, cy = _centred(y)
+        q, _ = _centred(q)
+        nr, nl = a.shape[0], y.shape[0]
+        if nl < 1 or q.shape[0] != nr + nl:
+            raise RuntimeError("dlpd: interface pair %d needs nl >= 1 ligand points and nr + nl static points" % p)
+        rec = mom[p]
+        rec[0:9] = _moment(a, q[:nr]).reshape(-1)
+        rec[9:18] = _moment(y, q[nr:]).reshape(-1)
+        rec[18:21] = _fsum_columns(q[nr:])
+        rec[21:24] = _fsum_columns(a) if nr else 0.0
+        rec[24:27] = _fsum_columns(y)
+        rec[27], rec[28], rec[29] = math.fsum((a * a).reshape(-1)), math.fsum((y * y).reshape(-1)), math.fsum((q * q).reshape(-1))
+        rec[30:33], rec[33:36] = ca, cy
+        rec[36:42] = _moment(y, y)[np.triu_indices(3)]
+        counts[p] = (nr, nl)
+    y, cy = _centred(ligand_ca)
+    z, cz = _centred(target_ca)
+    if y.shape[0] < 1 or y.shape != z.shape:
+        raise RuntimeError("dlpd: native_moments needs ligand_ca and target_ca of one shape (m, 3), m >= 1")
+    rec = mom[nI]
+    rec[0:9] = _moment(z, y).reshape(-1)
+    rec[9:12], rec[12:15] = _fsum_columns(y), _fsum_columns(z)
+    rec[15], rec[16] = math.fsum((y * y).reshape(-1)), math.fsum((z * z).reshape(-1))
+    rec[17:20], rec[20:23] = cy, cz
+    rec[23:29] = _moment(y, y)[np.triu_indices(3)]
+    counts[nI] = (0, y.shape[0])
+    return mom, counts
+
+
+def _poses64(poses, lib, device=None):
+    import numpy as np
+    if not torch.is_tensor(poses):
+        poses = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, dtype=np.float64)))
+    if device is not None:
+        poses = poses.to(device)
+    if not ((poses.is_cuda or lib is not None) and poses.dtype == torch.float64 and poses.dim() == 2 and poses.shape[1] == 12
+            and poses.shape[0] > 0):
+        raise RuntimeError("dlpd: poses must be (K, 12) float64 (R row-major, then t) on the device, K > 0; there is no CPU path")
+    return poses.contiguous()
+
+
+def _on(t, dtype, dev, name, lib):
+    if not (torch.is_tensor(t) and t.dtype == dtype and t.device == dev and (t.is_cuda or lib is not None)):
+        raise RuntimeError("dlpd: %s must be a %s tensor on the poses' device" % (name, str(dtype).replace("torch.", "")))
+    return t.contiguous()
+
+
+def pose_native_rmsd(poses, moments, counts, lib=None):
+    """(irmsd (K), lrmsd (K)) float64 on the poses' device: the interface RMSD (minimum over the interface pairs of the RMSD
+    after the best rigid superposition) and the ligand RMSD (no superposition) of K poses, from the moment block of
+    ``native_moments`` -- ``moments`` (nI + 1, 48) float64 on the device, ``counts`` (nI + 1, 2) host integers."""
+    import numpy as np
+    lib_ = lib or get_lib()
+    poses = _poses64(poses, lib)
+    moments = _on(moments, torch.float64, poses.device, "moments", lib)
+    counts = np.ascontiguousarray(np.asarray(counts, dtype=np.int32))
+    nI = counts.shape[0] - 1
+    if counts.ndim != 2 or counts.shape[1] != 2 or tuple(moments.shape) != (nI + 1, EVAL_REC):
+        raise RuntimeError("dlpd: pose_native_rmsd expects moments (nI + 1, %d) and counts (nI + 1, 2)" % EVAL_REC)
+    K = poses.shape[0]
+    irmsd = torch.empty(K, dtype=torch.float64, device=poses.device)
+    lrmsd = torch.empty(K, dtype=torch.float64, device=poses.device)
+    lib_.call("dlpd_pose_native_rmsd", _ptr(poses), K, _ptr(moments), counts.ctypes.data, nI, _ptr(irmsd), _ptr(lrmsd),
+              _stream(poses.device))
+    return irmsd, lrmsd
+
+
+def pose_native_contacts(poses, rec_atoms, lig_atoms, ranges, ranges_host, cutoff, lib=None):
+    """count (K) int32: how many of the C native contacts hold under each pose.  ``rec_atoms`` (NRa, 3) / ``lig_atoms`` (NLa, 3)
+    float32 on the device, residue-contiguous (the receptor's in the docking frame, the ligand's in its own); contact c is the
+    atom ranges rec [r0, r1) x lig [l0, l1): ``ranges`` (C, 4) int32 on the device, ``ranges_host`` the same array on the host
+    (the library checks that one); it holds iff some atom pair lies within ``cutoff`` (d^2 <= cutoff^2 in float32)."""
+    import numpy as np
+    lib_ = lib or get_lib()
+    poses = _poses64(poses, lib)
+    dev = poses.device
+    rec_atoms = _on(rec_atoms, torch.float32, dev, "rec_atoms", lib).reshape(-1, 3)
+    lig_atoms = _on(lig_atoms, torch.float32, dev, "lig_atoms", lib).reshape(-1, 3)
+    ranges = _on(ranges, torch.int32, dev, "ranges", lib).reshape(-1, 4)
+    ranges_host = np.ascontiguousarray(np.asarray(ranges_host, dtype=np.int32)).reshape(-1, 4)
+    C = ranges_host.shape[0]
+    if ranges.shape[0] != C:
+        raise RuntimeError("dlpd: ranges and ranges_host must hold the same (C, 4) contacts")
+    K = poses.shape[0]
+    count = torch.empty(K, dtype=torch.int32, device=dev)
+    lib_.call("dlpd_pose_native_contacts", _ptr(poses), K, _ptr(rec_atoms), rec_atoms.shape[0], _ptr(lig_atoms), lig_atoms.shape[0],
+              _ptr(ranges), ranges_host.ctypes.data, C, float(cutoff), _ptr(count), _stream(dev))
+    return count
+
+
+def pose_capri(count, irmsd, lrmsd, C, lib=None):
+    """(fnat (K) float64 = count / (C + 0.001), capri (K) int32): the class starts at 0 and is set to 1, 2, 3 by three
+    successive ifs ``(fnat >= a and lrmsd <= b) or irmsd <= c`` with (a, b, c) = (0.1, 10, 4), (0.3, 5, 2), (0.5, 1, 1)."""
+    lib_ = lib or get_lib()
+    dev = count.device
+    count = _on(count, torch.int32, dev, "count", lib)
+    irmsd, lrmsd = _on(irmsd, torch.float64, dev, "irmsd", lib), _on(lrmsd, torch.float64, dev, "lrmsd", lib)
+    K = count.shape[0]
+    if K == 0 or irmsd.shape[0] != K or lrmsd.shape[0] != K:
+        raise RuntimeError("dlpd: pose_capri expects count, irmsd and lrmsd of one length K > 0")
+    fnat = torch.empty(K, dtype=torch.float64, device=dev)
+    capri = torch.empty(K, dtype=torch.int32, device=dev)
+    lib_.call("dlpd_pose_capri", _ptr(count), _ptr(irmsd), _ptr(lrmsd), int(C), K, _ptr(fnat), _ptr(capri), _stream(dev))
+    return fnat, capri
+
+
+def pose_evaluate(poses, native, lib=None):
+    """(irmsd, lrmsd, fnat, capri) of K poses ((K, 12) float64: R row-major, then t in Angstrom, in the frame of a .dat file)
+    against ``native``, a ``Results.InterfaceSelection.NativeReference`` on the device the poses are on (an array of poses is
+    moved there).  Three launches on one stream; only K-sized results exist."""
+    poses = _poses64(poses, lib, device=native.device)
+    irmsd, lrmsd = pose_native_rmsd(poses, native.moments, native.counts, lib=lib)
+    count = pose_native_contacts(poses, native.rec_atoms, native.lig_atoms, native.ranges, native.ranges_host, native.contact_dist,
+                                 lib=lib)
+    fnat, capri = pose_capri(count, irmsd, lrmsd, native.C, lib=lib)
+    return irmsd, lrmsd, fnat, capri

@@ -554,6 +554,27 @@ size_t dlpd_pose_cluster_ws(int K);
 int dlpd_pose_cluster(const float* E, int K, float radius, int max_clusters, int* centres, int* sizes, int* labels, int* count,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* Evaluation of a list of poses against a native complex: what the reference's EvaluateBenchmark.py:95-113
+ * (interface RMSD) and processing_utils.py:183-236 (contacts, fnat, CAPRI class) compute pose by pose on the host.  A pose
+ * is 12 doubles, R row-major then t in Angstrom: it carries the bbox-centred unbound ligand's point y to R y + t, next to the
+ * bbox-centred unbound receptor (the frame of a .dat file).  K <= 65536, nI <= 16, NLa <= 2048, NRa <= 65536, C <= 65536
+ * (else DLPD_ERR_UNSUPPORTED); a null pointer, K <= 0, nI <= 0, a record with nl < 1 or nr < 0, a contact whose atom range is
+ * empty or leaves its array, a negative or NaN cutoff: DLPD_ERR_ARG; on an error nothing is launched and nothing is written.
+ * dlpd_pose_native_rmsd: moments holds nI interface records and then the L-RMSD record, 48 doubles each, on the device
+ *   (layout and formulas: csrc/dlpd_evaluate.h; packed by ops.native_moments); counts is a HOST array of (nI + 1) x (nr, nl)
+ *   int32, the point counts of the records (nr of the last is ignored).  irmsd[k] = the minimum over the nI pairs of the
+ *   superposed RMSD, lrmsd[k] = the RMSD of the ligand's points to their targets without superposition; all float64.
+ * dlpd_pose_native_contacts: rec_atoms (NRa, 3) / lig_atoms (NLa, 3) float32, residue-contiguous; contact c is the atom
+ *   ranges rec [r0, r1) x lig [l0, l1), ranges = (C, 4) int32 (r0, r1, l0, l1) on the device and ranges_host the same values in
+ *   host memory (the copy that is checked).  count[k] (int32) = the contacts with an atom pair at d^2 <= cutoff^2 in float32
+ *   under pose k (R, t rounded to float32 once).  C = 0 is allowed (every count 0).
+ * dlpd_pose_capri: fnat[k] = count[k] / (C + 0.001) (float64) and capri[k] (int32), the class cascade on (fnat, lrmsd, irmsd). */
+int dlpd_pose_native_rmsd(const double* poses, int K, const double* moments, const int* counts, int nI, double* irmsd, double* lrmsd,
+                          void* stream);
+int dlpd_pose_native_contacts(const double* poses, int K, const float* rec_atoms, int NRa, const float* lig_atoms, int NLa,
+                              const int* ranges, const int* ranges_host, int C, float cutoff, int* count, void* stream);
+int dlpd_pose_capri(const int* count, const double* irmsd, const double* lrmsd, int C, int K, double* fnat, int* capri, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

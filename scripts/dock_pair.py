@@ -14,6 +14,11 @@ without the benchmark table: representation -> exhaustive rotation x translation
                                            # one) by pose RMSD over the ligand's atoms, greedily in score order, RADIUS in Angstrom,
                                            # at most KEEP clusters (Docker.cluster) -> <out>.clustered.dat (the centres) and
                                            # <out>.clustered.sizes.txt (their populations, one per line) beside the .dat
+        [--native BOUND_REC.pdb BOUND_LIG.pdb]  # evaluate every pose against the native complex (Docker.evaluate: interface RMSD,
+                                           # ligand RMSD, fraction of native contacts, CAPRI class; receptor.pdb / ligand.pdb are
+                                           # the unbound structures) -> <out>.eval.txt, one line per pose of the .dat, and a
+                                           # summary; likewise <out>.refined.eval.txt / .minimized.eval.txt / .clustered.eval.txt
+                                           # for the lists of the steps that ran
 
 Multi-GPU: launch with torch.distributed.run; rotations are sharded over the ranks, rank 0 writes."""
 import argparse
@@ -51,6 +56,32 @@ def cluster_and_write(docker, prepared, out, radius, keep=None, poses=None, rank
     return name, sizes_name
 
 
+def evaluation_summary(ev):
+    """The best class and the lowest I-RMSD among the first 1 / 10 / 100 / all poses, and the rank of the first pose of class
+    >= 1 (1-based; None: there is none) -> (rows [(n, best class, lowest irmsd)], rank)"""
+    K = len(ev["capri"])
+    rows = [(n, int(ev["capri"][:n].max()), float(ev["irmsd"][:n].min())) for n in sorted(set(min(m, K) for m in (1, 10, 100, K))) if n]
+    hit = [k for k in range(K) if ev["capri"][k] >= 1]
+    return rows, (hit[0] + 1 if hit else None)
+
+
+def evaluate_and_write(docker, native, out, poses=None, tag="", rank=0):
+    """The --native step: ``Docker.evaluate`` on ``poses`` (None: the top list), then <out>[.tag].eval.txt (one line per pose:
+    irmsd lrmsd fnat capri) and the summary, by ``rank`` 0 (every rank evaluates the same gathered list)."""
+    ev = docker.evaluate(native, poses=poses)
+    name = (out[:-4] if out.endswith(".dat") else out) + ("." + tag if tag else "") + ".eval.txt"
+    if rank == 0:
+        docker.new_log(name, rewrite=True)
+        docker.write_evaluation()
+        docker.cleanup()
+        rows, first = evaluation_summary(ev)
+        print("wrote", name, "(%d poses against %d native contacts)" % (len(ev["capri"]), native.C))
+        for n, cls, irmsd in rows:
+            print("  top %-6d best CAPRI class %d, lowest I-RMSD %.3f A" % (n, cls, irmsd))
+        print("  first pose of class >= 1:", "rank %d" % first if first else "none")
+    return name
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("receptor")
@@ -70,6 +101,7 @@ def main():
     ap.add_argument("--minimize", default=None, type=int, metavar="STEPS")
     ap.add_argument("--minimize-translation", action="store_true")
     ap.add_argument("--cluster", default=None, metavar="RADIUS[:KEEP]")
+    ap.add_argument("--native", default=None, nargs=2, metavar=("BOUND_REC.pdb", "BOUND_LIG.pdb"))
     args = ap.parse_args()
     entry.build()
     from deeplocalproteindocking_amd.Docker import Docker
@@ -110,6 +142,11 @@ def main():
     docker.cleanup()
     if rank == 0:
         print("wrote", args.out, "(%d poses, best score %f)" % (len(docker.top_list), docker.top_list[0][4]))
+    native = None
+    if args.native is not None:
+        from deeplocalproteindocking_amd.Results.InterfaceSelection import native_reference
+        native = native_reference(args.native[0], args.native[1], args.receptor, args.ligand).to(dev)
+        evaluate_and_write(docker, native, args.out, rank=rank)
     if refine:
         from deeplocalproteindocking_amd.Utils.Rotations import local_perturbations
         docker.refine_prepared(prepared, perturbations=local_perturbations(refine[0], refine[1]), radius=refine[2])
@@ -119,6 +156,8 @@ def main():
             docker.write_refined_conformations()
             docker.cleanup()
             print("wrote", name, "(%d poses, best score %f)" % (len(docker.refined_list), docker.refined_list[0][2]))
+        if native is not None:
+            evaluate_and_write(docker, native, args.out, poses=docker.refined_list, tag="refined", rank=rank)
     if args.minimize is not None:
         docker.minimize_prepared(prepared, steps=args.minimize, translation=args.minimize_translation)
         if rank == 0:           # every rank minimised the same gathered list
@@ -127,10 +166,14 @@ def main():
             docker.write_refined_conformations()
             docker.cleanup()
             print("wrote", name, "(%d poses, best score %f)" % (len(docker.refined_list), docker.refined_list[0][2]))
+        if native is not None:
+            evaluate_and_write(docker, native, args.out, poses=docker.refined_list, tag="minimized", rank=rank)
     if args.cluster is not None:
         radius, keep = parse_cluster(args.cluster)
         last = docker.refined_list if (refine or args.minimize is not None) else None       # (None: the top list)
         cluster_and_write(docker, prepared, args.out, radius, keep, poses=last, rank=rank)
+        if native is not None:
+            evaluate_and_write(docker, native, args.out, poses=docker.clustered_list, tag="clustered", rank=rank)
     if world > 1:
         dist.destroy_process_group()
 
