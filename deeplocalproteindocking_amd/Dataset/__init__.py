@@ -1,7 +1,5 @@
-"""``from Dataset import get_benchmark_stream`` as the reference's local_test.py:8 does.  The
-training stream (SplitComplexDataset) is outside the docking path (out of scope)."""
+"""``from Dataset import get_benchmark_stream`` as the reference's local_test.py:8 does, and ``from Dataset import
+get_dataset_stream`` as its local_train.py:6 does; ``DecoySet`` writes the sets that stream reads."""
 from .SplitComplexBenchmark import get_benchmark_stream, read_pdb_list, read_dataset_list, SplitComplexBenchmark
-
-
-def get_dataset_stream(*args, **kwargs):
-    raise Exception("Dataset.get_dataset_stream: training data loading is out of scope of this build")
+from .SplitComplexDataset import get_dataset_stream, SplitComplexDataset, BatchSamplerQuality
+from .DecoySet import native_pose, near_native_poses, pose_entries, write_decoy_set

@@ -645,29 +645,45 @@ class Docker:
             out[k, :9], out[k, 9:] = r.reshape(-1), t
         return out
 
-    def evaluate(self, native, poses=None):
+    def evaluate(self, native, poses=None, fnonnat=False):
         """How good every pose of a list is (default: ``self.top_list``; ``refined_list`` and ``clustered_list`` entries are
         taken too; none of the lists is touched): ``native`` is a ``Results.InterfaceSelection.NativeReference`` of the target
         (``native_reference`` of the bound and unbound files).  -> ``self.evaluation``, a dict of numpy arrays aligned with
         the poses: ``irmsd`` and ``lrmsd`` in Angstrom, ``fnat`` (float64) and ``capri`` (int32, 0 incorrect .. 3 high).
+        ``fnonnat``: also ``fnonnat`` (float64, the share of the pose's residue contacts the native does not have), ``n_dec``
+        and ``n_corr`` (int32, ops.pose_contact_counts); ``native`` must then have been built with ``all_contacts=True``.
         At most 65,536 poses.  Every rank evaluates the same (gathered) list; there is no collective here."""
         from deeplocalproteindocking_amd import ops
         poses = list(self.top_list if poses is None else poses)
         self.evaluation = {"irmsd": np.zeros(0), "lrmsd": np.zeros(0), "fnat": np.zeros(0), "capri": np.zeros(0, dtype=np.int32)}
+        if fnonnat:
+            if getattr(native, "all", None) is None:
+                raise RuntimeError("dlpd: Docker.evaluate(fnonnat=True) needs a native reference built with all_contacts=True")
+            self.evaluation.update({"fnonnat": np.zeros(0), "n_dec": np.zeros(0, dtype=np.int32), "n_corr": np.zeros(0, dtype=np.int32)})
         if not poses:
             return self.evaluation
-        got = ops.pose_evaluate(self.dat_frame_poses(poses), native.to(self.device), lib=self._lib)
+        P = self.dat_frame_poses(poses)
+        got = ops.pose_evaluate(P, native.to(self.device), lib=self._lib)
         self.evaluation = {k: v.cpu().numpy() for k, v in zip(("irmsd", "lrmsd", "fnat", "capri"), got)}
+        if fnonnat:
+            n_dec, n_corr = ops.pose_contact_counts(P, native, lib=self._lib)
+            self.evaluation.update({"fnonnat": ops.fnonnat_of(n_dec, n_corr).cpu().numpy(), "n_dec": n_dec.cpu().numpy(),
+                                    "n_corr": n_corr.cpu().numpy()})
         return self.evaluation
 
     def write_evaluation(self):
-        """``self.evaluation`` into the open log, one line per pose: irmsd, lrmsd, fnat (``%f``) and the class, tab-separated"""
+        """``self.evaluation`` into the open log, one line per pose: irmsd, lrmsd, fnat (``%f``) and the class, tab-separated;
+        an evaluation that carries ``fnonnat`` writes it (``%f``) as a fifth column"""
         if self.log is None:
             return
         ev = getattr(self, "evaluation", None)
         if ev is not None and len(ev["capri"]):
-            self.log.write("\n".join("%f\t%f\t%f\t%d" % (i, l, f, c) for i, l, f, c in
-                                     zip(ev["irmsd"], ev["lrmsd"], ev["fnat"], ev["capri"])) + "\n")
+            if "fnonnat" in ev:
+                self.log.write("\n".join("%f\t%f\t%f\t%d\t%f" % (i, l, f, c, g) for i, l, f, c, g in
+                                         zip(ev["irmsd"], ev["lrmsd"], ev["fnat"], ev["capri"], ev["fnonnat"])) + "\n")
+            else:
+                self.log.write("\n".join("%f\t%f\t%f\t%d" % (i, l, f, c) for i, l, f, c in
+                                         zip(ev["irmsd"], ev["lrmsd"], ev["fnat"], ev["capri"])) + "\n")
         self.log.flush()
 
     def refine_prepared(self, prepared, perturbations=None, radius=1, poses=None):

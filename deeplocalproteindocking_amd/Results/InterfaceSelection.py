@@ -296,9 +296,12 @@ class NativeReference(object):
     ``ranges`` (C, 4) int32 with its host copy ``ranges_host``; ``C``; ``contact_dist``.  On the host: ``interfaces`` (the
     selections of ``unbound_interfaces``), ``pairs`` (the interface point sets), ``ligand_ca`` / ``target_ca`` (the points of the
     ligand RMSD), ``superposition`` (Q, s: bound frame -> docking frame), ``contacts`` (the transferred residue pairs) and
-    ``rec_atoms64`` / ``lig_atoms64``.  ``to(device)`` moves the first group."""
+    ``rec_atoms64`` / ``lig_atoms64``.  ``to(device)`` moves the first group.
+    Built with ``all_contacts`` it also carries ``all``, the tables of ops.contact_tables (every atom of both structures,
+    residue offsets, bounding spheres, the native pairs as a bitmap) for ops.pose_contact_counts; ``to`` moves them too."""
 
     def __init__(self, **kw):
+        self.all = None
         self.__dict__.update(kw)
         self.device = torch.device("cpu")
         self.moments = torch.from_numpy(self.moments_host)
@@ -309,29 +312,67 @@ class NativeReference(object):
     def to(self, device):
         for name in ("moments", "rec_atoms", "lig_atoms", "ranges"):
             setattr(self, name, getattr(self, name).to(device))
+        if self.all is not None:
+            for name in ALL_CONTACT_TENSORS:
+                self.all[name] = self.all[name].to(device)
         self.device = self.moments.device
         return self
 
 
-def native_reference_from_points(pairs, ligand_ca, target_ca, rec_atoms, lig_atoms, ranges, contact_dist=5.0, **host):
+ALL_CONTACT_TENSORS = ("rec_atoms", "rec_off", "rec_sph", "lig_atoms", "lig_off", "lig_sph", "native_bits")
+
+
+def native_reference_from_points(pairs, ligand_ca, target_ca, rec_atoms, lig_atoms, ranges, contact_dist=5.0, all_rec=None,
+                                 all_lig=None, all_pairs=None, **host):
     """A ``NativeReference`` from explicit point sets (``native_reference`` without the PDB files): the arguments of
-    ops.native_moments, the two interface atom arrays (float64, residue-contiguous) and the contacts' atom ranges (C, 4)."""
+    ops.native_moments, the two interface atom arrays (float64, residue-contiguous) and the contacts' atom ranges (C, 4).
+    ``all_rec`` / ``all_lig``: (atoms (n, 3), offsets (nres + 1)) of EVERY atom of the two structures, residue-contiguous, in
+    the same frames, and ``all_pairs``: the native pairs as (receptor residue, ligand residue) indices into them -- all three
+    or none; with them the reference serves ops.pose_contact_counts."""
     from deeplocalproteindocking_amd import ops
     moments, counts = ops.native_moments(pairs, ligand_ca, target_ca)
     ranges = np.ascontiguousarray(np.asarray(ranges, dtype=np.int32).reshape(-1, 4))
+    if (all_rec is None) != (all_lig is None) or (all_rec is None) != (all_pairs is None):
+        raise RuntimeError("dlpd: all_rec, all_lig and all_pairs go together")
+    tables = None if all_rec is None else ops.contact_tables(all_rec[0], all_rec[1], all_lig[0], all_lig[1], all_pairs)
     return NativeReference(moments_host=moments, counts=counts, rec_atoms64=np.asarray(rec_atoms, dtype=np.float64).reshape(-1, 3),
                            lig_atoms64=np.asarray(lig_atoms, dtype=np.float64).reshape(-1, 3), ranges_host=ranges, C=int(ranges.shape[0]),
-                           contact_dist=float(contact_dist), pairs=pairs, ligand_ca=ligand_ca, target_ca=target_ca, **host)
+                           contact_dist=float(contact_dist), pairs=pairs, ligand_ca=ligand_ca, target_ca=target_ca, all=tables, **host)
 
 
-def native_reference(bound_receptor, bound_ligand, unbound_receptor, unbound_ligand, contact_dist=5.0):
+def _all_residues(s):
+    """the residues ``native_contact_pairs`` sees (standard amino acids, no insertion code), in file order"""
+    seen, order = set(), []
+    for i in np.nonzero(_standard(s))[0]:
+        key = (str(s["chain"][i]), int(s["resnum"][i]))
+        if key not in seen:
+            seen.add(key)
+            order.append(_residue(s, i))
+    return order
+
+
+def _packed_standard_atoms(s, shift):
+    """every ATOM record of every residue of ``_all_residues``, residue after residue -> (atoms (n, 3), offsets, {(chain,
+    resnum): index})"""
+    residues = _all_residues(s)
+    rows, off = [], [0]
+    for res in residues:
+        rows.append(_residue_atoms(s, res, shift))                                      # (as the interface arrays take them)
+        off.append(off[-1] + len(rows[-1]))
+    atoms = np.concatenate(rows) if rows else np.zeros((0, 3))
+    return atoms, np.asarray(off, dtype=np.int32), {(r[0], r[1]): k for k, r in enumerate(residues)}
+
+
+def native_reference(bound_receptor, bound_ligand, unbound_receptor, unbound_ligand, contact_dist=5.0, all_contacts=False):
     """Everything the evaluation of one target's poses needs (structures as ``read_structure`` gives them, or file names).
     The docking frame: each unbound structure about its own bounding-box centre, the ligand then placed by the pose.
       I-RMSD   the interface pairs of ``unbound_interfaces``, C-alpha, as ``evaluate_target`` selects them;
       L-RMSD   every aligned ligand residue with a C-alpha in both structures; the bound ligand's are carried into the docking
                frame by the Kabsch fit of the bound receptor's aligned C-alphas onto the unbound receptor's;
       fnat     ``native_contact_pairs`` of the bound complex, transferred (``transfer_pairs``); per contact all ATOM records of
-               the two unbound residues."""
+               the two unbound residues;
+      fnonnat  (``all_contacts``) every ATOM record of every standard residue of the two unbound structures, and the
+               transferred contacts as a set over them."""
     br, bl, ur, ul = (read_structure(s) if isinstance(s, str) else s for s in (bound_receptor, bound_ligand, unbound_receptor, unbound_ligand))
     shift_r, shift_l = -bbox_centre(ur), -bbox_centre(ul)
     interfaces = unbound_interfaces(br, bl, ur, ul, contact_dist)
@@ -352,8 +393,13 @@ def native_reference(bound_receptor, bound_ligand, unbound_receptor, unbound_lig
     rec_atoms, rec_at = _packed_atoms(ur, sorted(set(c[0] for c in contacts)), shift_r)
     lig_atoms, lig_at = _packed_atoms(ul, sorted(set(c[1] for c in contacts)), shift_l)
     ranges = [rec_at[r] + lig_at[l] for r, l in contacts]
+    extra = {}
+    if all_contacts:
+        ra, ro, rindex = _packed_standard_atoms(ur, shift_r)
+        la, lo, lindex = _packed_standard_atoms(ul, shift_l)
+        extra = dict(all_rec=(ra, ro), all_lig=(la, lo), all_pairs=[(rindex[r[:2]], lindex[l[:2]]) for r, l in contacts])
     return native_reference_from_points(pairs, ligand_ca, target_ca, rec_atoms, lig_atoms, ranges, contact_dist, interfaces=interfaces,
-                                        superposition=(Q, s), contacts=contacts, bound_contacts=bound_pairs)
+                                        superposition=(Q, s), contacts=contacts, bound_contacts=bound_pairs, **extra)
 
 
 def conformation_poses(conformations):

@@ -127,6 +127,7 @@ SIGNATURES = {
     "dlpd_pose_native_rmsd": (_i, [_p, _i, _p, _p, _i, _p, _p, _p]),
     "dlpd_pose_native_contacts": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _f, _p, _p]),
     "dlpd_pose_capri": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
+    "dlpd_pose_contacts_all": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _p]),
 }
 
 ERRORS = {1: "DLPD_ERR_ARG (bad pointer/size)", 2: "DLPD_ERR_UNSUPPORTED (size not compiled)",

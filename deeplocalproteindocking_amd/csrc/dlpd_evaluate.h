@@ -164,6 +164,37 @@ __global__ void __launch_bounds__(EVAL_NT) k_pose_native_rmsd(const double* __re
   }
 }
 
+// The contact predicate, shared with k_pose_contacts_all (dlpd_contacts.h): the pose rounded to float32 once, a posed atom by
+// one fma chain per coordinate, d^2 by one fma chain over the three differences, d2 <= r2.
+DLPD_D void eval_pose32(const double* __restrict__ P, float* R, float* t) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) R[i] = (float)P[i];
+#pragma unroll
+  for (int i = 0; i < 3; i++) t[i] = (float)P[9 + i];
+}
+// p = R y + t: the chain t -> fma(R0, x, .) -> fma(R1, y, .) -> fma(R2, z, .) per coordinate
+DLPD_D void eval_pose_point(const float* R, const float* t, const float* __restrict__ y, float* p) {
+  const float x = y[0], yy = y[1], z = y[2];
+#pragma unroll
+  for (int i = 0; i < 3; i++) p[i] = __fmaf_rn(R[3 * i + 2], z, __fmaf_rn(R[3 * i + 1], yy, __fmaf_rn(R[3 * i], x, t[i])));
+}
+// some atom pair of rec [r0, r1) x posed [l0, l1) has d^2 <= r2
+DLPD_D bool eval_ranges_touch(const float* __restrict__ rec, int r0, int r1, const float* posed, int l0, int l1, float r2) {
+  for (int i = r0; i < r1; i++) {
+    const float a[3] = {rec[3 * i], rec[3 * i + 1], rec[3 * i + 2]};
+    for (int j = l0; j < l1; j++) {
+      float d2 = 0.f;
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+        const float d = a[q] - posed[3 * j + q];
+        d2 = __fmaf_rn(d, d, d2);
+      }
+      if (d2 <= r2) return true;
+    }
+  }
+  return false;
+}
+
 // one pose per block; CAP: the posed ligand's room in LDS
 template <int CAP>
 __global__ void __launch_bounds__(EVAL_CONTACT_NT) k_pose_native_contacts(const double* __restrict__ poses, const float* __restrict__ rec,
@@ -172,36 +203,15 @@ __global__ void __launch_bounds__(EVAL_CONTACT_NT) k_pose_native_contacts(const 
   __shared__ float posed[CAP * 3];
   __shared__ int s_cnt[EVAL_CONTACT_NT / 64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const double* P = poses + (size_t)blockIdx.x * 12;
   float R[9], t[3];
-#pragma unroll
-  for (int i = 0; i < 9; i++) R[i] = (float)P[i];
-#pragma unroll
-  for (int i = 0; i < 3; i++) t[i] = (float)P[9 + i];
-  for (int j = tid; j < NLa; j += EVAL_CONTACT_NT) {
-    const float x = lig[3 * j], y = lig[3 * j + 1], z = lig[3 * j + 2];
-#pragma unroll
-    for (int i = 0; i < 3; i++) posed[3 * j + i] = __fmaf_rn(R[3 * i + 2], z, __fmaf_rn(R[3 * i + 1], y, __fmaf_rn(R[3 * i], x, t[i])));
-  }
+  eval_pose32(poses + (size_t)blockIdx.x * 12, R, t);
+  for (int j = tid; j < NLa; j += EVAL_CONTACT_NT) eval_pose_point(R, t, lig + 3 * j, posed + 3 * j);
   __syncthreads();
   int n = 0;
   for (int c = tid; c < C; c += EVAL_CONTACT_NT) {
     const int r0 = max(ranges[4 * c], 0), r1 = min(ranges[4 * c + 1], NRa);       // (clamped: never outside the arrays)
     const int l0 = max(ranges[4 * c + 2], 0), l1 = min(ranges[4 * c + 3], NLa);
-    bool hit = false;
-    for (int i = r0; i < r1 && !hit; i++) {
-      const float a[3] = {rec[3 * i], rec[3 * i + 1], rec[3 * i + 2]};
-      for (int j = l0; j < l1; j++) {
-        float d2 = 0.f;
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-          const float d = a[q] - posed[3 * j + q];
-          d2 = __fmaf_rn(d, d, d2);
-        }
-        if (d2 <= r2) { hit = true; break; }
-      }
-    }
-    n += hit ? 1 : 0;
+    n += eval_ranges_touch(rec, r0, r1, posed, l0, l1, r2) ? 1 : 0;
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m);

@@ -573,3 +573,6 @@ int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int*
 
 // evaluation of the finished list against a native complex: I-RMSD, L-RMSD, native contacts, CAPRI class
 #include "dlpd_evaluate.h"
+
+// every residue contact of the posed complex, for fnonnat: shares the predicate of dlpd_evaluate.h
+#include "dlpd_contacts.h"

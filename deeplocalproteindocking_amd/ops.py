@@ -1302,3 +1302,100 @@ def pose_evaluate(poses, native, lib=None):
                                  lib=lib)
     fnat, capri = pose_capri(count, irmsd, lrmsd, native.C, lib=lib)
     return irmsd, lrmsd, fnat, capri
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Every residue contact of a posed complex: n_dec, n_corr and fnonnat (csrc/dlpd_contacts.h)
+# ----------------------------------------------------------------------------------------------------------------------
+CONT_MAX_LIGAND_ATOMS, CONT_MAX_LIGAND_RESIDUES = 8192, 1024
+CONT_MAX_RECEPTOR_ATOMS, CONT_MAX_RECEPTOR_RESIDUES = 65536, 8192
+
+
+def _round_up32(x):
+    """the least float32 >= x that is safely above it (a float32 conversion rounds down by half a step at most)"""
+    import numpy as np
+    return np.nextafter(np.asarray(x, dtype=np.float64).astype(np.float32), np.float32(np.inf))
+
+
+def _bounding_spheres(atoms32, off):
+    """(nres, 4) float32: the centroid of every residue's float32 atoms, rounded to float32, and a radius, rounded UP, that
+    covers them about that rounded centre (float64 on the float32 values); an empty residue: zeros"""
+    import numpy as np
+    a64 = atoms32.astype(np.float64)
+    out = np.zeros((len(off) - 1, 4), dtype=np.float32)
+    for i in range(len(off) - 1):
+        x = a64[off[i]:off[i + 1]]
+        if len(x):
+            c = x.mean(axis=0).astype(np.float32)
+            out[i, :3] = c
+            out[i, 3] = _round_up32(np.sqrt(((x - c.astype(np.float64)) ** 2).sum(axis=1)).max())
+    return out
+
+
+def contact_tables(rec_atoms, rec_off, lig_atoms, lig_off, native_pairs):
+    """What ``pose_contact_counts`` reads of one target, packed once on the host: ``rec_atoms`` (NRa, 3) / ``lig_atoms``
+    (NLa, 3) float32, every atom, residue-contiguous (receptor in the docking frame, ligand in its own); ``rec_off`` /
+    ``lig_off`` int32 residue offsets with their host copies; ``rec_sph`` (NRres, 4) / ``lig_sph`` (NLres + 1, 4) bounding
+    spheres (the last ligand row: the whole ligand); ``lig_extent``; ``native_bits``: the native pairs -- (receptor residue,
+    ligand residue) indices, a pair named twice counts once -- as a bitmap over (lambda, rho), int32 words.  -> dict (tensors
+    on the CPU)."""
+    import numpy as np
+    ra = np.ascontiguousarray(np.asarray(rec_atoms, dtype=np.float64).reshape(-1, 3).astype(np.float32))
+    la = np.ascontiguousarray(np.asarray(lig_atoms, dtype=np.float64).reshape(-1, 3).astype(np.float32))
+    ro = np.ascontiguousarray(np.asarray(rec_off, dtype=np.int32).reshape(-1))
+    lo = np.ascontiguousarray(np.asarray(lig_off, dtype=np.int32).reshape(-1))
+    nr, nl = len(ro) - 1, len(lo) - 1
+    if nr < 1 or nl < 1 or ro[0] != 0 or lo[0] != 0 or ro[-1] != len(ra) or lo[-1] != len(la) or (np.diff(ro) < 0).any() or (np.diff(lo) < 0).any() \
+            or not len(ra) or not len(la):
+        raise RuntimeError("dlpd: contact_tables needs non-empty atom arrays and offsets 0 = off[0] <= ... <= off[nres] = natoms")
+    rs, ls = _bounding_spheres(ra, ro), _bounding_spheres(la, lo)
+    ls = np.concatenate([ls, _bounding_spheres(la, np.array([0, len(la)]))])
+    extent = float(_round_up32(max(np.sqrt((la.astype(np.float64) ** 2).sum(axis=1)).max(), np.sqrt((ls[:, :3].astype(np.float64) ** 2).sum(axis=1)).max())))
+    W = (nr + 31) // 32
+    bits = np.zeros(nl * W, dtype=np.uint32)
+    for rho, lam in native_pairs:
+        if not (0 <= rho < nr and 0 <= lam < nl):
+            raise RuntimeError("dlpd: native pair (%d, %d) outside the %d x %d residues" % (rho, lam, nr, nl))
+        bits[lam * W + (rho >> 5)] |= np.uint32(1 << (rho & 31))
+    t = torch.from_numpy
+    return {"rec_atoms": t(ra), "rec_off": t(ro), "rec_sph": t(rs), "lig_atoms": t(la), "lig_off": t(lo), "lig_sph": t(np.ascontiguousarray(ls)),
+            "native_bits": t(bits.view(np.int32)), "rec_off_host": ro.copy(), "lig_off_host": lo.copy(), "lig_extent": extent,
+            "n_native": int(sum(bin(int(w)).count("1") for w in bits))}
+
+
+def pose_contact_counts(poses, native, lib=None):
+    """(n_dec (K), n_corr (K)) int32 on the poses' device: under each pose the number of residue pairs of the two unbound
+    structures with an atom pair within ``native.contact_dist`` -- every atom of both, the predicate of ``pose_native_contacts``
+    bit for bit -- and how many of them are native pairs.  ``native``: a NativeReference built with ``all_contacts=True``."""
+    tb = getattr(native, "all", None)
+    if tb is None:
+        raise RuntimeError("dlpd: pose_contact_counts needs a native reference built with all_contacts=True")
+    lib_ = lib or get_lib()
+    poses = _poses64(poses, lib, device=native.device)
+    dev = poses.device
+    ra, la = _on(tb["rec_atoms"], torch.float32, dev, "rec_atoms", lib), _on(tb["lig_atoms"], torch.float32, dev, "lig_atoms", lib)
+    ro, lo = _on(tb["rec_off"], torch.int32, dev, "rec_off", lib), _on(tb["lig_off"], torch.int32, dev, "lig_off", lib)
+    rs, ls = _on(tb["rec_sph"], torch.float32, dev, "rec_sph", lib), _on(tb["lig_sph"], torch.float32, dev, "lig_sph", lib)
+    bits = _on(tb["native_bits"], torch.int32, dev, "native_bits", lib)
+    roh, loh = tb["rec_off_host"], tb["lig_off_host"]
+    NRa, NLa, NRres, NLres = ra.shape[0], la.shape[0], roh.shape[0] - 1, loh.shape[0] - 1
+    if ro.numel() != NRres + 1 or lo.numel() != NLres + 1 or tuple(rs.shape) != (NRres, 4) or tuple(ls.shape) != (NLres + 1, 4) \
+            or bits.numel() != NLres * ((NRres + 31) // 32) or int(roh[-1]) != NRa or int(loh[-1]) != NLa:
+        raise RuntimeError("dlpd: the all-contacts tables of this native reference do not belong together")
+    K = poses.shape[0]
+    n_dec = torch.empty(K, dtype=torch.int32, device=dev)
+    n_corr = torch.empty(K, dtype=torch.int32, device=dev)
+    lib_.call("dlpd_pose_contacts_all", _ptr(poses), K, _ptr(ra), _ptr(ro), _ptr(rs), NRa, NRres, _ptr(la), _ptr(lo), _ptr(ls), NLa, NLres,
+              roh.ctypes.data, loh.ctypes.data, _ptr(bits), float(tb["lig_extent"]), float(native.contact_dist), _ptr(n_dec), _ptr(n_corr),
+              _stream(dev))
+    return n_dec, n_corr
+
+
+def fnonnat_of(n_dec, n_corr):
+    """(n_dec - n_corr) / (n_dec + 0.001) in float64: ``_get_fnat``'s second value (processing_utils.py:219-224)"""
+    return (n_dec - n_corr).double() / (n_dec.double() + 0.001)
+
+
+def pose_fnonnat(poses, native, lib=None):
+    """fnonnat (K) float64 on the poses' device: the share of a pose's residue contacts that the native complex does not have"""
+    return fnonnat_of(*pose_contact_counts(poses, native, lib=lib))

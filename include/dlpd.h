@@ -575,6 +575,25 @@ int dlpd_pose_native_contacts(const double* poses, int K, const float* rec_atoms
                               const int* ranges, const int* ranges_host, int C, float cutoff, int* count, void* stream);
 int dlpd_pose_capri(const int* count, const double* irmsd, const double* lrmsd, int C, int K, double* fnat, int* capri, void* stream);
 
+/* Every residue contact of the posed complex: the ``dec`` set that processing_utils.py:183-216 finds per decoy
+ * with a neighbour search over all atoms of both proteins, counted, and its overlap with the native set -- the two integers
+ * fnonnat = (n_dec - n_corr) / (n_dec + 0.001) (_get_fnat, :219-224) is made of.  Poses and frames as above.
+ * rec_atoms (NRa, 3) / lig_atoms (NLa, 3) float32: ALL atoms, residue-contiguous; rec_off (NRres + 1) / lig_off (NLres + 1)
+ * int32: residue i owns atoms [off[i], off[i + 1]); rec_off_host / lig_off_host: the same values in host memory (the copies that
+ * are checked: non-decreasing, inside the arrays).  rec_sph (NRres, 4) / lig_sph (NLres + 1, 4) float32: per residue a centre
+ * and a radius, rounded up, that covers its atoms; the last row of lig_sph covers the whole ligand; lig_extent >= |y|_2 of
+ * every ligand atom and centre (what the filter's padding is derived from: csrc/dlpd_contacts.h).  native_bits: the native
+ * pairs as a bitmap, bit (rho & 31) of word lambda * ceil(NRres / 32) + (rho >> 5), NLres * ceil(NRres / 32) words.
+ * n_dec[k] = the residue pairs (rho, lambda) with an atom pair at d^2 <= cutoff^2 in float32 under pose k -- the predicate of
+ * dlpd_pose_native_contacts, bit for bit -- and n_corr[k] = those of them whose bit is set (both int32).
+ * K <= 65536, NLa <= 8192, NLres <= 1024, NRa <= 65536, NRres <= 8192 (else DLPD_ERR_UNSUPPORTED); a null pointer, K < 0, an
+ * empty structure, offsets out of order, a negative or NaN cutoff or extent: DLPD_ERR_ARG; K = 0 is a no-op.  On an error
+ * nothing is launched and nothing is written. */
+int dlpd_pose_contacts_all(const double* poses, int K, const float* rec_atoms, const int* rec_off, const float* rec_sph, int NRa,
+                           int NRres, const float* lig_atoms, const int* lig_off, const float* lig_sph, int NLa, int NLres,
+                           const int* rec_off_host, const int* lig_off_host, const unsigned* native_bits, float lig_extent,
+                           float cutoff, int* n_dec, int* n_corr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

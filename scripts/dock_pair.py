@@ -19,6 +19,11 @@ without the benchmark table: representation -> exhaustive rotation x translation
                                            # the unbound structures) -> <out>.eval.txt, one line per pose of the .dat, and a
                                            # summary; likewise <out>.refined.eval.txt / .minimized.eval.txt / .clustered.eval.txt
                                            # for the lists of the steps that ran
+        [--decoys DIR[:NEAR[:FAR]]]        # with --native: write a training set for this target under DIR in the layout
+                                           # Dataset.get_dataset_stream reads (Dataset.DecoySet): NEAR poses round the native one
+                                           # (default 10) and the first FAR poses (default 10) of the list the run ends with -- the
+                                           # clustered one if --cluster was given, else the top list -- each labelled by
+                                           # Docker.evaluate(fnonnat=True); the target is named after <out>
 
 Multi-GPU: launch with torch.distributed.run; rotations are sharded over the ranks, rank 0 writes."""
 import argparse
@@ -82,6 +87,30 @@ def evaluate_and_write(docker, native, out, poses=None, tag="", rank=0):
     return name
 
 
+def parse_decoys(spec):
+    """DIR[:NEAR[:FAR]] -> (dataset directory, poses round the native, poses of the run's last list)"""
+    part = spec.split(":")
+    return part[0], (int(part[1]) if len(part) > 1 and part[1] else 10), (int(part[2]) if len(part) > 2 and part[2] else 10)
+
+
+def decoys_and_write(docker, native, dataset_dir, out, receptor, ligand, poses=None, near=10, far=10, seed=0, subset="training_set.dat",
+                     rank=0):
+    """The --decoys step: ``near`` poses round the native one and the first ``far`` entries of ``poses`` (None: the top list),
+    evaluated with ``fnonnat=True`` and written as one target of a training set under ``dataset_dir`` by ``rank`` 0
+    -> the path of the target's table."""
+    from deeplocalproteindocking_amd.Dataset.DecoySet import near_native_poses, pose_entries, write_decoy_set
+    entries = pose_entries(near_native_poses(native, near, seed=seed), docker) if near > 0 else []
+    entries += list(docker.top_list if poses is None else poses)[:far]
+    ev = docker.evaluate(native, poses=entries, fnonnat=True)
+    target = os.path.basename(out[:-4] if out.endswith(".dat") else out)
+    if rank != 0:
+        return os.path.join(dataset_dir, "Description", "%s.dat" % target)
+    table = write_decoy_set(dataset_dir, target, receptor, ligand, docker.dat_frame_poses(entries), ev, subset=subset)
+    print("wrote", table, "(%d decoys, %d of class >= 1, fnonnat %.3f .. %.3f)" %
+          (len(entries), int((ev["capri"] >= 1).sum()), float(ev["fnonnat"].min()), float(ev["fnonnat"].max())))
+    return table
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("receptor")
@@ -102,7 +131,10 @@ def main():
     ap.add_argument("--minimize-translation", action="store_true")
     ap.add_argument("--cluster", default=None, metavar="RADIUS[:KEEP]")
     ap.add_argument("--native", default=None, nargs=2, metavar=("BOUND_REC.pdb", "BOUND_LIG.pdb"))
+    ap.add_argument("--decoys", default=None, metavar="DIR[:NEAR[:FAR]]")
     args = ap.parse_args()
+    if args.decoys is not None and args.native is None:
+        ap.error("--decoys needs --native (the decoys are labelled against the native complex)")
     entry.build()
     from deeplocalproteindocking_amd.Docker import Docker
     from deeplocalproteindocking_amd.Models import (E3MultiResRepr4x4, GlobalDockingModel, SE3MultiResReprScalar,
@@ -145,7 +177,7 @@ def main():
     native = None
     if args.native is not None:
         from deeplocalproteindocking_amd.Results.InterfaceSelection import native_reference
-        native = native_reference(args.native[0], args.native[1], args.receptor, args.ligand).to(dev)
+        native = native_reference(args.native[0], args.native[1], args.receptor, args.ligand, all_contacts=args.decoys is not None).to(dev)
         evaluate_and_write(docker, native, args.out, rank=rank)
     if refine:
         from deeplocalproteindocking_amd.Utils.Rotations import local_perturbations
@@ -174,6 +206,10 @@ def main():
         cluster_and_write(docker, prepared, args.out, radius, keep, poses=last, rank=rank)
         if native is not None:
             evaluate_and_write(docker, native, args.out, poses=docker.clustered_list, tag="clustered", rank=rank)
+    if args.decoys is not None:
+        ddir, near, far = parse_decoys(args.decoys)
+        decoys_and_write(docker, native, ddir, args.out, args.receptor, args.ligand,
+                         poses=docker.clustered_list if args.cluster is not None else None, near=near, far=far, rank=rank)
     if world > 1:
         dist.destroy_process_group()
 
