@@ -21,7 +21,7 @@ What differs underneath:
     replaced by the fused kernels only when that is what the model computes -- the reference's
     ``GlobalDockingModel.forward`` with an MLP ``SimpleFilter`` (``Models.fused_filter_parameters``).
     Any other model / filter module is CALLED, on volumes rotated and correlated by the stand-alone
-    HIP ops, followed by the device top-K (``_dock_volumes_generic``);
+    HIP ops, followed by the device top-K (``_search_unfused``);
   * atoms come from ``Utils.FullAtom.CoordsBackend`` (PDB reader, 11-type typing, GPU density
     projection; TorchProteinLibrary itself is absent, SURVEY.md 8f rows 1,3), created on first use;
     ``coords_backend=`` swaps in another implementation;
@@ -209,7 +209,7 @@ class Docker:
         if rotation_center is not None:
             self.conventions = VolumeConventions.from_dict(dict(self.conventions.to_dict(), rotation_center=rotation_center))
         self._ops_cache = {}
-        # box sizes without a compiled plan: on the fused kernels inside the next compiled box (_dock_volumes_embedded);
+        # box sizes without a compiled plan: on the fused kernels inside the next compiled box (_search_plan);
         # False: the plan-free stand-alone ops (ops.VolumeConvolution._forward_generic), any box up to 128
         self.embed_uncompiled_boxes = True
         # dockE3 on the fused engine: a plugin with occupancy maps does not write the tiles it skips (the engine goes by the
@@ -994,35 +994,34 @@ class Docker:
         R_all = self.rot.R
         ids = self.shard(R_all.shape[0]) if rot_indices is None else np.asarray(rot_indices, dtype=np.int64)
         params = fused_filter_parameters(model)
+        if receptor_forbidden is None:          # no clash exclusion: the ligand's side of the channel is never read
+            ligand_forbidden = clash_provider = None
         # prepared: a PreparedPair whose engine already holds this receptor's spectrum and this ligand (Docker.prepare)
         pre_eng = prepared.engine if prepared is not None else None
-        eng = pre_eng if pre_eng is not None else self._make_engine(rec, receptor_forbidden, nb, params)
-        entries = None
-        if eng is None and self.embed_uncompiled_boxes and not self._library().call("dlpd_grid_supported", int(L)):
-            entries = self._dock_volumes_embedded(rec, lig, receptor_forbidden, ligand_forbidden, nb, ids,
-                                                  clash_provider, params)
-        if entries is not None:
-            self.path = "embedded"
-        else:
-            self.path = "fused" if eng is not None else ("ops" if self._ops_path_ok(rec, params) else "call")
-        if entries is not None:
-            pass
-        elif eng is not None:
-            two_res = eng.C1 > 0
+        path, eng, Lc = self._search_plan(rec, receptor_forbidden, params, nb, pre_eng)
+        if eng is not None:
             if pre_eng is None:
-                eng.set_ligand(lig[0], ligand_forbidden if ligand_forbidden is not None else torch.zeros(L, L, L),
-                               lig[1] if two_res else None)
+                # (embedded: the volumes in the corner of the Lc^3 box, the batch's re-projected clash volumes likewise)
+                fit = (lambda v, s=1: self._embed(torch.as_tensor(v, dtype=torch.float32), Lc // s)) if Lc else (lambda v, s=1: v)
+                lf = ligand_forbidden if ligand_forbidden is not None else torch.zeros(L, L, L)
+                eng.set_ligand(fit(lig[0]), fit(torch.as_tensor(lf).reshape(L, L, L)), fit(lig[1], 2) if eng.C1 > 0 else None)
             eng.clash_provider = clash_provider
+            if Lc and clash_provider is not None:
+                forb_e = torch.zeros(nb, Lc, Lc, Lc, dtype=torch.float32, device=self.device)
+
+                def provider(Rb):          # (Docker.py:221-224)
+                    n = Rb.shape[0]
+                    forb_e[:n, :L, :L, :L] = clash_provider(Rb).reshape(n, L, L, L)
+                    return forb_e[:n]
+                eng.clash_provider = provider
             eng.reset_top()
-            eng.search(R_all[ids], rot_ids=ids)
-            self.engine = eng
+            eng.search(R_all[ids], rot_ids=ids)          # (embedded: the engine's top-K works on the gathered (2L)^3 grid)
             entries = eng.top_entries()
-        elif self.path == "ops":
-            entries = self._dock_volumes_multires(rec, lig, receptor_forbidden, ligand_forbidden, nb, ids,
-                                                  clash_provider, params)
+            if Lc:
+                eng.clash_provider = None                # (it holds the Lc^3 buffers)
         else:
-            entries = self._dock_volumes_generic(rec, lig, receptor_forbidden, ligand_forbidden,
-                                                 int(model_batch or nb), ids, clash_provider)
+            entries = self._search_unfused(path, rec, receptor_forbidden, ids, nb if path == "ops" else int(model_batch or nb),
+                                           self._rotated_ligand(lig, ligand_forbidden, clash_provider), params)
         entries = self._gather(entries)
         self.top_list = DeviceTopList.to_top_list(entries, 2 * L)
         if write:
@@ -1051,7 +1050,7 @@ class Docker:
         # one engine (multi-GB workspaces, side stream, top-list buffers) serves every pair of the same shape:
         # local_test.py docks hundreds of targets with one Docker
         C, C1, has_clash = rec[0].shape[0], (rec[1].shape[0] if two_res else 0), receptor_forbidden is not None
-        # inner_box: the volumes are inner_box^3 boxes in the corner of the L^3 ones (_dock_volumes_embedded): pivots and
+        # inner_box: the volumes are inner_box^3 boxes in the corner of the L^3 ones (_search_plan): pivots and
         # crop of the rotation are the small box's
         Lp = int(inner_box or L)
         cv = self.conventions
@@ -1099,54 +1098,43 @@ class Docker:
                     return Lc
         return None
 
-    def _dock_volumes_embedded(self, rec, lig, rec_forb, lig_forb, batch_size, ids, clash_provider, params):
-        """A box size without a compiled plan on the FUSED kernels (box_size is a free argument of the reference,
+    def _search_plan(self, rec, receptor_forbidden, params, nb, prepared_engine=None):
+        """Which code searches this receptor -> (path, eng, Lc); the one writer of ``self.path``, ``self.engine_box`` and, for a
+        pooled engine, ``self.engine``.
+          fused     ``DockingEngine`` on the box's own compiled plan (``prepared_engine``, or ``_make_engine``): eng, Lc None;
+          embedded  the same engine on the next compiled box Lc, the volumes in its corner (below): eng, Lc;
+          ops       the stand-alone ops + the HIP filter kernel (``_ops_path_ok``): eng None;
+          call      the model really called, whatever module it is: eng None.
+        embedded -- a box size without a compiled plan on the FUSED kernels (box_size is a free argument of the reference,
         Docker.py:18,22-24,31): the L^3 volumes sit in the corner of the next compiled box Lc^3, zeros around them.
         The correlation of two L-sized volumes is linear for every translation |t| < L on any grid of at least 2L
         points, so the 2Lc grid holds the reference's (2L)^3 grid exactly: index t for 0 <= t <= L (t = L: no overlap,
         zero -- the reference's wrap plane) and 2Lc + t for -L < t < 0.  The engine rotates the embedded ligand about the
         SMALL box's pivot and crops the result to the small box (K1's ``extent``, include/dlpd.h), so a batch costs what
         it costs at box Lc; the scores of the reference's grid are gathered out of the larger one -- monotonic in every
-        index, so ties keep the reference's order -- for the device top-K.  None when no compiled box fits or the model's
-        scoring is not the fused MLP."""
-        if params is None:
-            return None
+        index, so ties keep the reference's order -- for the device top-K.  Taken with ``embed_uncompiled_boxes`` when the
+        model's scoring is the fused MLP, over one resolution or the L, L/2 pair, and a compiled box fits."""
         L = rec[0].shape[-1]
-        two_res = len(rec) == 2 and rec[1].shape[-1] * 2 == L
-        if not (len(rec) == 1 or two_res):
-            return None
-        Lc = self._embedding_box(L, two_res)
-        if Lc is None:
-            return None
-        dev = self.device
-
-        embed = self._embed
-        has_clash = rec_forb is not None
-        rec_e = [embed(rec[0], Lc)] + ([embed(rec[1], Lc // 2)] if two_res else [])
-        rf_e = embed(torch.as_tensor(rec_forb, dtype=torch.float32).reshape(L, L, L), Lc) if has_clash else None
-        eng = self._make_engine(rec_e, rf_e, batch_size, params, inner_box=L)
+        eng, Lc = prepared_engine, None
         if eng is None:
-            return None
+            eng = self._make_engine(rec, receptor_forbidden, nb, params)
+        two_res = len(rec) == 2 and rec[1].shape[-1] * 2 == L
+        if eng is None and params is not None and self.embed_uncompiled_boxes and (len(rec) == 1 or two_res) and \
+                not self._library().call("dlpd_grid_supported", int(L)):
+            Lc = self._embedding_box(L, two_res)
+            if Lc is not None:
+                rf = receptor_forbidden
+                if rf is not None:
+                    rf = self._embed(torch.as_tensor(rf, dtype=torch.float32).reshape(L, L, L), Lc)
+                eng = self._make_engine([self._embed(rec[0], Lc)] + ([self._embed(rec[1], Lc // 2)] if two_res else []), rf, nb,
+                                        params, inner_box=L)
+                Lc = Lc if eng is not None else None
+        if eng is not None:
+            self.path, self.engine = ("embedded" if Lc else "fused"), eng
+        else:
+            self.path = "ops" if self._ops_path_ok(rec, params) else "call"
         self.engine_box = Lc
-        lf_e = None
-        if has_clash:
-            lf_e = embed(torch.as_tensor(lig_forb, dtype=torch.float32).reshape(L, L, L), Lc) if clash_provider is None \
-                else torch.zeros(Lc, Lc, Lc)
-        eng.set_ligand(embed(lig[0], Lc), lf_e, embed(lig[1], Lc // 2) if two_res else None)
-        forb_e = torch.zeros(batch_size, Lc, Lc, Lc, dtype=torch.float32, device=dev) if clash_provider is not None else None
-
-        def provider(Rb):          # the re-projected clash volumes of the batch (Docker.py:221-224), into the corner of Lc^3
-            n = Rb.shape[0]
-            forb_e[:n, :L, :L, :L] = clash_provider(Rb).reshape(n, L, L, L)
-            return forb_e[:n]
-
-        eng.clash_provider = provider if clash_provider is not None else None
-        eng.reset_top()
-        eng.search(self.rot.R[ids], rot_ids=ids)          # the engine's top-K works on the gathered (2L)^3 grid (engine.window)
-        self.engine = eng
-        entries = eng.top_entries()
-        eng.clash_provider = None
-        return entries
+        return self.path, eng, Lc
 
     @staticmethod
     def _ops_path_ok(rec, params):
@@ -1154,83 +1142,73 @@ class Docker:
         <= 64 over one or two resolutions (dlpd_filter_mask)."""
         return params is not None and params[0].shape[0] <= 64 and len(rec) <= 2
 
-    def _batch_inputs(self, rec, lig, rec_forb, lig_forb, clash_provider):
-        dev = self.device
-        L = rec[0].shape[-1]
-        rec_d = [v.to(dev) for v in rec]
-        lig_d = [v.to(dev) for v in lig]
-        rf = lf = None
-        if rec_forb is not None:
-            rf = torch.as_tensor(rec_forb, dtype=torch.float32).reshape(1, 1, L, L, L).to(dev)
-            if clash_provider is None:
-                lf = torch.as_tensor(lig_forb, dtype=torch.float32).reshape(1, 1, L, L, L).to(dev)
-        return rec_d, lig_d, rf, lf
-
-    def _dock_volumes_multires(self, rec, lig, rec_forb, lig_forb, batch_size, ids, clash_provider=None, params=None):
-        """Reference-shaped loop on the stand-alone ops: rotate, clash correlation, per-resolution
-        correlation, HIP filter kernel (upsample + concat + MLP + mask multiply), device top-K."""
-        from deeplocalproteindocking_amd.ops import VolumeConvolution, VolumeRotation, filter_volumes
-        dev = self.device
-        model = self.docking_model
-        emb = self.embed_uncompiled_boxes
-        rotate, conv_noclip = _PivotRotation(self), VolumeConvolution(lib=self._lib, embed=emb)
+    def _convolutions(self):
+        """-> (convolve, conv_noclip) of the unfused paths: the model's own correlation -- the reference's op with its clip and
+        this Docker's box policy and clip convention, or whatever else ``model.convolve`` is -- and the plain one of the clash
+        channel (Docker.py:32)."""
+        from deeplocalproteindocking_amd.ops import VolumeConvolution
+        model, emb = self.docking_model, self.embed_uncompiled_boxes
         convolve = getattr(model, "convolve", None) or VolumeConvolution(clip=getattr(model, "clip", 5.0), lib=self._lib)
-        if isinstance(convolve, VolumeConvolution):        # the reference's op: same clip, this Docker's box policy
+        if isinstance(convolve, VolumeConvolution):
             convolve = VolumeConvolution(clip=convolve.clip, lib=self._lib, embed=emb, clip_mode=self.conventions.clip_mode)
-        rec_d, lig_d, rf, lf = self._batch_inputs(rec, lig, rec_forb, lig_forb, clash_provider)
-        L = rec[0].shape[-1]
-        top = DeviceTopList(self.max_conf, batch_size, dev, self._library())
-        top.reset()
-        has_clash = rec_forb is not None
-        R_all = self.rot.R
-        W1, b1, W2, b2 = params if params is not None else fused_filter_parameters(model)
-        for beg in range(0, len(ids), batch_size):
-            bid = ids[beg:beg + batch_size]
-            nb = len(bid)
-            Rb = R_all[bid].to(device=dev, dtype=torch.float32).contiguous()
-            lig_rot = [rotate(v.unsqueeze(0).expand(nb, -1, -1, -1, -1).contiguous(), Rb) for v in lig_d]
-            rec_b = [v.unsqueeze(0).expand(nb, -1, -1, -1, -1).contiguous() for v in rec_d]
-            convolved = [convolve(r, l) for r, l in zip(rec_b, lig_rot)]
-            norm = None
-            if has_clash:
-                lfr = (clash_provider(Rb).reshape(nb, 1, L, L, L).contiguous() if clash_provider is not None
-                       else rotate(lf.expand(nb, -1, -1, -1, -1).contiguous(), Rb))
-                norm = conv_noclip(rf.expand(nb, -1, -1, -1, -1).contiguous(), lfr).squeeze(1).contiguous()
-            V = filter_volumes(convolved, W1, b1, W2, float(b2.reshape(-1)[0]), mask_norm=norm,
-                               threshold=model.threshold_clash, lib=self._lib)
-            top.select(V.reshape(nb, -1), nb)
-            top.merge(torch.as_tensor(bid, dtype=torch.int32).to(dev), nb)
-        return top.entries()
+        return convolve, VolumeConvolution(lib=self._lib, embed=emb)
 
-    def _dock_volumes_generic(self, rec, lig, rec_forb, lig_forb, batch_size, ids, clash_provider=None):
-        """The loop body of Docker.py:218-232 with the scoring model really CALLED --
-        ``V = self.docking_model(receptor_volumes, ligand_volumes_rotated)`` (Docker.py:229), whatever
-        module that is -- between the stand-alone HIP ops (volume rotation, clash correlation) and the
-        device top-K.  This is the path of a user-defined filter / docking model."""
-        from deeplocalproteindocking_amd.ops import VolumeConvolution, VolumeRotation
-        dev = self.device
-        model = self.docking_model
-        rotate, conv_noclip = _PivotRotation(self), VolumeConvolution(lib=self._lib, embed=self.embed_uncompiled_boxes)
-        rec_d, lig_d, rf, lf = self._batch_inputs(rec, lig, rec_forb, lig_forb, clash_provider)
+    def _rotated_ligand(self, lig, ligand_forbidden=None, clash_provider=None):
+        """``_search_unfused``'s ligand source for a search on volumes: the stored ligand volumes rotated by the stand-alone op;
+        the forbidden volume re-projected by ``clash_provider(Rb)`` or the stored one rotated the same way (neither: no clash)."""
+        dev, rotate = self.device, _PivotRotation(self)
+        L = lig[0].shape[-1]
+        lig_d = [v.to(dev) for v in lig]
+        lf = None
+        if ligand_forbidden is not None and clash_provider is None:
+            lf = torch.as_tensor(ligand_forbidden, dtype=torch.float32).reshape(1, 1, L, L, L).to(dev)
+
+        def ligand_batch(bid, Rb):
+            nb = len(bid)
+            forb = None
+            if clash_provider is not None:
+                forb = clash_provider(Rb).reshape(nb, 1, L, L, L).contiguous()
+            elif lf is not None:
+                forb = rotate(lf.expand(nb, -1, -1, -1, -1).contiguous(), Rb)
+            return [rotate(v.unsqueeze(0).expand(nb, -1, -1, -1, -1).contiguous(), Rb) for v in lig_d], forb
+        return ligand_batch
+
+    def _search_unfused(self, path, rec, receptor_forbidden, ids, nbatch, ligand_batch, params):
+        """The loop body of Docker.py:218-232 / :163-177 between the stand-alone HIP ops and the device top-K, ``nbatch``
+        rotations at a time -> the list's entries.  ``ligand_batch(bid, Rb)`` -> the batch's ligand volumes and its forbidden
+        volume ((nb, 1, L, L, L); None without clash).  Only the scoring goes by ``path``:
+          ops   per-resolution correlation, then the HIP filter kernel (upsample + concat + MLP + mask multiply);
+          call  ``V = self.docking_model(receptor_volumes, ligand_volumes)`` (Docker.py:229) really CALLED, whatever module
+                that is -- the path of a user-defined filter / docking model -- then the mask multiply."""
+        from deeplocalproteindocking_amd.ops import filter_volumes
+        dev, model = self.device, self.docking_model
         L = rec[0].shape[-1]
-        top = DeviceTopList(self.max_conf, batch_size, dev, self._library())
+        convolve, conv_noclip = self._convolutions()
+        rec_d = [v.to(dev) for v in rec]
+        rf = None
+        if receptor_forbidden is not None:
+            rf = torch.as_tensor(receptor_forbidden, dtype=torch.float32).reshape(1, 1, L, L, L).to(dev)
+        top = DeviceTopList(self.max_conf, nbatch, dev, self._library())
         top.reset()
-        has_clash = rec_forb is not None
-        R_all = self.rot.R
         with torch.no_grad():
-            for beg in range(0, len(ids), batch_size):
-                bid = ids[beg:beg + batch_size]
+            for beg in range(0, len(ids), nbatch):
+                bid = ids[beg:beg + nbatch]
                 nb = len(bid)
-                Rb = R_all[bid].to(device=dev, dtype=torch.float32).contiguous()
-                lig_rot = [rotate(v.unsqueeze(0).expand(nb, -1, -1, -1, -1).contiguous(), Rb) for v in lig_d]
+                Rb = self.rot.R[bid].to(device=dev, dtype=torch.float32).contiguous()
+                lig_b, forb = ligand_batch(bid, Rb)
                 rec_b = [v.unsqueeze(0).expand(nb, -1, -1, -1, -1).contiguous() for v in rec_d]
-                V = model(rec_b, lig_rot).reshape(nb, 2 * L, 2 * L, 2 * L).to(torch.float32)
-                if has_clash:
-                    lfr = (clash_provider(Rb).reshape(nb, 1, L, L, L).contiguous() if clash_provider is not None
-                           else rotate(lf.expand(nb, -1, -1, -1, -1).contiguous(), Rb))
-                    norm = conv_noclip(rf.expand(nb, -1, -1, -1, -1).contiguous(), lfr).squeeze(1)
-                    V = torch.lt(norm, model.threshold_clash).to(dtype=torch.float32) * V
-                V = V.contiguous()
+                norm = None
+                if rf is not None:
+                    norm = conv_noclip(rf.expand(nb, -1, -1, -1, -1).contiguous(), forb).squeeze(1).contiguous()
+                if path == "ops":
+                    W1, b1, W2, b2 = params
+                    V = filter_volumes([convolve(r, l) for r, l in zip(rec_b, lig_b)], W1, b1, W2, float(b2.reshape(-1)[0]),
+                                       mask_norm=norm, threshold=model.threshold_clash, lib=self._lib)
+                else:
+                    V = model(rec_b, lig_b).reshape(nb, 2 * L, 2 * L, 2 * L).to(torch.float32)
+                    if norm is not None:
+                        V = torch.lt(norm, model.threshold_clash).to(dtype=torch.float32) * V
+                    V = V.contiguous()
                 top.select(V.reshape(nb, -1), nb)
                 top.merge(torch.as_tensor(bid, dtype=torch.int32).to(dev), nb)
         return top.entries()
@@ -1362,52 +1340,22 @@ class Docker:
         """Docker.py:135-182: the ligand is rotated in coordinate space and re-projected and
         re-represented every batch (the plugin's cost), then scored by the same kernels: the fused
         engine takes the batch's volumes as they are (no volume rotation); the stand-alone ops, or a
-        call of the model itself, where the engine has no layout for the model (see dock_volumes).
-        The two halves of a batch run one after the other on the caller's stream (``_dockE3_fused``)."""
+        call of the model itself, where the engine has no layout for the model (``_search_plan``).
+        The two halves of a batch run one after the other on the caller's stream (``_dockE3_fused``).
+        ``batch_size`` only sizes the calls of a model that has to be called, as in ``dockSE3``."""
         be = self._need_backend()
-        from deeplocalproteindocking_amd.ops import VolumeConvolution, filter_volumes
         self.top_list = []
         model = self.docking_model
         model.eval()
-        dev = self.device
+        dev, L = self.device, self.box_size
         self._share_random_rotation()
         p = self._prepared_for(prepared, ureceptor, uligand, "E3")
         ids = self.shard(self.rot.R.shape[0])
-        L = self.box_size
         with torch.no_grad():
-            receptor, receptor_volumes = p.receptor, p.receptor_volumes
             lc, ln, lo = p.ligand_atoms
-            rec = [v.reshape((-1,) + tuple(v.shape[-3:])) for v in receptor_volumes]
+            rec = [v.reshape((-1,) + tuple(v.shape[-3:])) for v in p.receptor_volumes]
             params = fused_filter_parameters(model)
-            eng = p.engine
-            Lc = None
-            if eng is None and params is not None and self.embed_uncompiled_boxes and \
-                    not self._library().call("dlpd_grid_supported", int(L)):
-                # a box without a compiled plan: the batch's volumes in the corner of the next compiled box, scored by
-                # the same engine; its top-K stage gathers the reference's grid (see _dock_volumes_embedded)
-                two_res = len(rec) == 2 and rec[1].shape[-1] * 2 == L
-                Lc = self._embedding_box(L, two_res) if (len(rec) == 1 or two_res) else None
-                if Lc is not None:
-                    eng = self._make_engine([self._embed(rec[0], Lc)] + ([self._embed(rec[1], Lc // 2)] if two_res else []),
-                                            self._embed(receptor.sum(dim=1)[0], Lc), self.launch_batch, params, inner_box=L)
-                    Lc = Lc if eng is not None else None
-                    self.engine_box = Lc
-            self.path = ("embedded" if Lc else "fused") if eng is not None else ("ops" if self._ops_path_ok(rec, params) else "call")
-            nbatch = self.launch_batch if self.path != "call" else int(batch_size)
-            if eng is not None:
-                eng.reset_top()
-                self.engine = eng
-            else:
-                emb = self.embed_uncompiled_boxes
-                conv_noclip = VolumeConvolution(lib=self._lib, embed=emb)
-                convolve = getattr(model, "convolve", None) or VolumeConvolution(clip=getattr(model, "clip", 5.0),
-                                                                                 lib=self._lib)
-                if isinstance(convolve, VolumeConvolution):
-                    convolve = VolumeConvolution(clip=convolve.clip, lib=self._lib, embed=emb,
-                                                 clip_mode=self.conventions.clip_mode)
-                top = DeviceTopList(self.max_conf, nbatch, dev, self._library())
-                top.reset()
-                receptor_forbidden = receptor.sum(dim=1).unsqueeze(dim=1).contiguous()
+            path, eng, Lc = self._search_plan(rec, p.receptor_forbidden, params, self.launch_batch, p.engine)
 
             def represent(bid):
                 """rotate + translate + project in one kernel (Docker.py:163-165), then the plugin (Docker.py:166-167)"""
@@ -1419,34 +1367,23 @@ class Docker:
                 # the forbidden volume = the sum over the atom types (Docker.py:169): projected once more with the types summed in
                 # the accumulator (33 MB) instead of a pass over the eleven volumes -- the integer sum of the types' fixed-point
                 # densities converted once: equal to it bit for bit while every type stays below 4 per voxel (accumulator < 2^24,
-                # each type's own float conversion is exact); above that the two differ by float32 rounding of either
+                # each type's own float conversion is exact); above that the two differ by float32 rounding of either.  Only the
+                # fused loop takes it; the unfused one sums the volumes as the reference does
                 ligand.dlpd_type_sum = be.project(lc, ln, lo, L, self.resolution, dev, R=Rb, shift=self.box_center, sum_types=True)[:, 0]
                 return ligand, model.representation(ligand)
 
-            batches = [ids[beg:beg + nbatch] for beg in range(0, len(ids), nbatch)]
             if eng is not None:
-                self._dockE3_fused(eng, batches, represent, Lc, nbatch)
-                batches = []
-            for bid in batches:
-                nb = len(bid)
-                ligand, ligand_volumes = represent(bid)
-                bid_dev = torch.as_tensor(bid, dtype=torch.int32).to(dev)
-                ligand_forbidden = ligand.sum(dim=1).unsqueeze(dim=1).contiguous()
-                norm = conv_noclip(receptor_forbidden.expand(nb, -1, -1, -1, -1).contiguous(), ligand_forbidden)
-                norm = norm.squeeze(1).contiguous()
-                rec_b = [v.expand(nb, -1, -1, -1, -1).contiguous() for v in receptor_volumes]
-                if self.path == "ops":
-                    W1, b1, W2, b2 = params
-                    convolved = [convolve(r, l) for r, l in zip(rec_b, ligand_volumes)]
-                    V = filter_volumes(convolved, W1, b1, W2, float(b2.reshape(-1)[0]), mask_norm=norm,
-                                       threshold=model.threshold_clash, lib=self._lib)
-                else:                                              # Docker.py:171-175 with the model called
-                    V = model(rec_b, ligand_volumes).reshape(nb, 2 * L, 2 * L, 2 * L).to(torch.float32)
-                    V = (torch.lt(norm, model.threshold_clash).to(dtype=torch.float32) * V).contiguous()
-                top.select(V.reshape(nb, -1), nb)
-                top.merge(bid_dev, nb)
-        entries = self._gather(eng.top_entries() if eng is not None else top.entries())
-        self.top_list = DeviceTopList.to_top_list(entries, 2 * self.box_size)
+                nbatch = self.launch_batch
+                eng.reset_top()
+                self._dockE3_fused(eng, [ids[beg:beg + nbatch] for beg in range(0, len(ids), nbatch)], represent, Lc, nbatch)
+                entries = eng.top_entries()
+            else:
+                def ligand_batch(bid, Rb):
+                    ligand, ligand_volumes = represent(bid)
+                    return ligand_volumes, ligand.sum(dim=1, keepdim=True)
+                entries = self._search_unfused(path, rec, p.receptor_forbidden, ids,
+                                               self.launch_batch if path == "ops" else int(batch_size), ligand_batch, params)
+        self.top_list = DeviceTopList.to_top_list(self._gather(entries), 2 * L)
         self.write_conformations()
 
     def _dockE3_fused(self, eng, batches, represent, Lc, nbatch):

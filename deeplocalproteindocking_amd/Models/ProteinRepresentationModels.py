@@ -26,7 +26,9 @@ hand-over for a user who has se3cnn: the eight dense (cout, cin, 5, 5, 5) kernel
 module names (``dense_kernel_contract``), used as they are -- the scalar-field SE3Convolution is a plain conv3d with that
 kernel, so the representation then IS the reference's.
 """
+import contextlib
 import os
+import threading
 import warnings
 
 import torch
@@ -42,6 +44,11 @@ def _torch_conv_allowed(what):
     raise RuntimeError("dlpd: %s has no HIP kernel (supported: cubic float32 volumes up to 80^3, kernel 3 or 5 with "
                        "padding k//2, stride 1 or 2, no bias, output channels a multiple of 16; MaxPool3d(5, 2, 2)). "
                        "Set DLPD_ALLOW_TORCH_CONV=1 to run it on torch/MIOpen instead." % what)
+
+
+# the modules THIS thread has inside ``outputs_with_maps()``: per thread, and outside the module, because a sweep prepares the
+# next target's receptor -- a forward of the same module -- on a second host thread while the search holds the context open
+_with_maps = threading.local()
 
 
 def _hip_inference(x, hip_lib):
@@ -122,19 +129,15 @@ class E3MultiResRepr4x4(Module):
     # undefined where the map is 0 -- only for a consumer that goes by the map (the fused engine's volumes path,
     # DockingEngine.step(occupancy=...); Docker._dockE3_fused is the one caller).  Outside the context every voxel is written.
     supports_unwritten_outputs = True
-    _unwritten = False
 
+    @contextlib.contextmanager
     def outputs_with_maps(self):
-        import contextlib
-
-        @contextlib.contextmanager
-        def ctx():
-            old, self._unwritten = self._unwritten, True
-            try:
-                yield self
-            finally:
-                self._unwritten = old
-        return ctx()
+        old = getattr(_with_maps, "modules", ())
+        _with_maps.modules = old + (self,)
+        try:
+            yield self
+        finally:
+            _with_maps.modules = old
 
     def _run(self, seq, x, occ=None, return_occupancy=False, unwritten=False):
         """The Sequential.  GPU inference: Conv3d(+ReLU) pairs and the max-pool on the HIP kernels (exact f32 on
@@ -195,7 +198,7 @@ class E3MultiResRepr4x4(Module):
         return (x, occ if sparse else None) if return_occupancy else x
 
     def forward(self, volume):
-        uw = self._unwritten
+        uw = any(m is self for m in getattr(_with_maps, "modules", ()))
         # an input that comes with its map (CoordsBackend.project(cells=True)): the first layer takes the map instead of
         # making one, and -- the input being unwritten outside its cells -- must go by it
         occ0 = getattr(volume, "dlpd_occupancy", None)

@@ -166,7 +166,7 @@ class DockingEngine:
         """coarse_channels > 0: the reference's two-resolution layout -- C channels at L^3 plus
         ``coarse_channels`` at (L/2)^3 (ProteinRepresentationModels.py:72-76); W1 is (H, C+coarse).
         extent < L: the volumes are extent^3 boxes in the corner of the L^3 ones (a box size without a compiled plan
-        inside this one, Docker._dock_volumes_embedded): rotated ligand volumes are cropped to that box (coarse grid:
+        inside this one, Docker._search_plan): rotated ligand volumes are cropped to that box (coarse grid:
         extent / 2), ``center`` / ``coarse_center`` are the pivots of the small boxes."""
         self.device = torch.device(device)
         if lib is None:

@@ -1,5 +1,5 @@
 """A box size WITHOUT a compiled plan (box_size is a free argument of the reference): throughput of the search on the
-fused kernels inside the next compiled box (Docker._dock_volumes_embedded, the default) against the plan-free stand-alone
+fused kernels inside the next compiled box (Docker._search_plan, the default) against the plan-free stand-alone
 ops (embed_uncompiled_boxes = False), same ranked list.  [16 @ L^3, 32 @ (L/2)^3], K = 2000.
     bench_embedded_box.py [box=72] [rotations=512] [rotations of the slow path=32]"""
 import os as _os; _os.environ.setdefault("DLPD_ALLOW_GENERATED_ROTATIONS", "1")

@@ -485,6 +485,43 @@ def check_plugin(lib, device, D, which=None):
         assert all(torch.isnan(u[e]).all() and not u.dlpd_occupancy[e].any() and not d[e].any() for d, u in zip(dense, uw))
 
 
+def check_outputs_with_maps_is_per_thread(lib, device, D=13):
+    """``outputs_with_maps()`` entered on one thread leaves a forward of the SAME module on another thread dense (a sweep
+    prepares the next receptor on a second host thread while the search holds the context open), and still holds on its own
+    thread afterwards.  One worker, started and joined inside the context: nothing here depends on timing."""
+    import threading
+    rep = plugin(lib, device)
+    xh, names = supports(D, which=("corner",))                     # (one voxel: most tiles stay empty, so NaNs can be left)
+    x = xh.to(device)
+    with torch.no_grad():
+        before = rep(x)
+    got = {}
+
+    def worker():                                                  # (grad mode is per thread too: a new thread starts with it on)
+        try:
+            with torch.no_grad(), _NanEmpty():
+                got["volumes"] = rep(x)
+        except BaseException as e:
+            got["error"] = e
+    with rep.outputs_with_maps():
+        t = threading.Thread(target=worker)
+        t.start()
+        t.join()
+        with torch.no_grad(), _NanEmpty():
+            uw = rep(x)
+    assert "error" not in got, got.get("error")
+    assert len(got["volumes"]) == len(before) == len(uw) == 2
+    for b, w in zip(before, got["volumes"]):
+        assert torch.equal(w, b) and not bool(torch.isnan(w).any())
+    nan_left = False
+    for d, u in zip(before, uw):                                   # the main thread is still inside: maps, NaNs outside them
+        assert torch.equal(u.dlpd_occupancy.cpu(), host_map(d))
+        live = _cells(u.dlpd_occupancy, d.shape[2]).expand_as(d)
+        assert torch.equal(u[live], d[live]) and bool((d[~live] == 0).all())
+        nan_left |= bool(torch.isnan(u).any())
+    assert nan_left
+
+
 def check_plugin_on_projected_protein(lib, device, L, res):
     """A CoordsBackend.project(cells=True) volume -- unwritten outside the cells the atoms' windows reach, with a map that
     COVERS its non-zero cells -- of a synthetic protein under three oblique rotations, one of which swings most atoms out of

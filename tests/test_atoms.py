@@ -272,9 +272,11 @@ def _dock_reference_shape(be, model, frec, flig, R, L, res, K, randR=None):
     return top, scale
 
 
-def _dock_reference_shape_e3(be, model, frec, flig, R, L, res, K):
+def _dock_reference_shape_e3(be, model, frec, flig, R, L, res, K, called=False):
     """The reference loop of Docker.dockE3 (Docker.py:135-182) restated with the oracle pieces: rotate the
-    ATOMS, project, represent, correlate -- no volume rotation."""
+    ATOMS, project, represent, correlate -- no volume rotation.  ``called``: the scores come from the filter MODULE, whatever
+    it is, called on the clipped correlations' features (GlobalDockingModel.forward's data movement, DockingModels.py:70-83,
+    as in ``_oracle_list_with_filter``) instead of the oracle's MLP."""
     centre = torch.full((1, 3), L * res / 2.0, dtype=torch.double)
 
     def load(f):
@@ -286,8 +288,8 @@ def _dock_reference_shape_e3(be, model, frec, flig, R, L, res, K):
     lc, ln_, lo = load(flig)
     rec = torch.from_numpy(orc.project_atoms(rc[0].numpy(), rn_[0].numpy(), ro[0].numpy(), L, res,
                                              shift=centre[0].numpy())).float()[None]
-    W = [w.cpu() for w in model.filter.parameters_tuple()]
-    top, scale = [], 0.0
+    W = None if called else [w.cpu() for w in model.filter.parameters_tuple()]
+    top, scale, N = [], 0.0, 2 * L
     with torch.no_grad():
         rv = model.representation(rec)
         for ri in range(R.shape[0]):
@@ -295,7 +297,15 @@ def _dock_reference_shape_e3(be, model, frec, flig, R, L, res, K):
                                                      shift=centre[0].numpy())).float()[None]
             lv = model.representation(lig)
             mask, _ = orc.clash_mask(rec.sum(dim=1, keepdim=True), lig.sum(dim=1, keepdim=True), model.threshold_clash)
-            V = (mask * orc.score_volumes(rv, lv, *W, clip=5.0))[0].contiguous()
+            if called:
+                conv = [orc.correlate_fft(r, l, clip=5.0) for r, l in zip(rv, lv)]
+                conv = [c.repeat_interleave(N // c.shape[2], 2).repeat_interleave(N // c.shape[2], 3)
+                        .repeat_interleave(N // c.shape[2], 4) for c in conv]
+                feat = torch.cat(conv, dim=1).permute(0, 2, 3, 4, 1).reshape(N * N * N, -1)
+                S = model.filter(feat).reshape(1, N, N, N)
+            else:
+                S = orc.score_volumes(rv, lv, *W, clip=5.0)
+            V = (mask * S)[0].contiguous()
             scale = max(scale, float(V.abs().max()))
             idx, sc = orc.rotation_picks_fast(V.numpy(), K)
             x, y, z = orc.flat_to_xyz(idx, 2 * L)
@@ -709,6 +719,48 @@ def test_hidden_width_above_32_takes_the_ops_path_on_gpu():
     import __graft_entry__ as entry
     entry.build()
     _run_wide_hidden(None, torch.device("cuda:0"))
+
+
+def _run_dockE3_unfused(tmp_path, lib, device, path):
+    """Docker.dockE3 where the fused engine has no layout for the model -- hidden width 40 at box 32 (``ops``) or a
+    user-defined filter (``call``) -- against the oracle restatement of Docker.py:135-182, in the band of the fused dockE3
+    tests: the same batch loop as ``dock_volumes``' unfused paths, fed from re-projected atoms."""
+    from deeplocalproteindocking_amd.Docker import Docker
+    from deeplocalproteindocking_amd.Models import GlobalDockingModel, SimpleFilter
+    L, res, K = 32, 1.25, 20
+    frec, _, _, _ = _typed(tmp_path, 14, seed=5)
+    flig, _, _, _ = _typed(tmp_path, 9, seed=6)
+    repr_ = _TinyRepr(4)
+    if path == "ops":
+        torch.manual_seed(81)
+        filt = SimpleFilter([4])
+        filt.fc[0], filt.fc[2] = torch.nn.Linear(4, 40), torch.nn.Linear(40, 1)
+        model = _Model(repr_, filt, thr=3.0)
+    else:
+        torch.manual_seed(5)
+        model = GlobalDockingModel(repr_, _GatedFilter(4), threshold_clash=3.0, lib=lib)
+    R = _three_rotations()
+    be = CoordsBackend(lib=lib)
+    want, scale = _dock_reference_shape_e3(be, model, frec, flig, R, L, res, K, called=(path == "call"))     # (on the host)
+    dk = Docker(model.to(device), box_size=L, resolution=res, max_conf=K, rotations=R, device=device, coords_backend=be, lib=lib)
+    with torch.no_grad():
+        dk.dockE3(frec, flig, batch_size=2)
+    assert dk.path == path and (path == "call" or dk.engine is None)
+    _assert_scores_are_informative(want)
+    _check_lists(dk.top_list, want, scale, K)
+
+
+@pytest.mark.parametrize("path", ["ops", "call"])
+def test_dockE3_off_the_fused_engine_emulated(emu, tmp_path, path):
+    _run_dockE3_unfused(tmp_path, emu, "cpu", path)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ["ops", "call"])
+def test_dockE3_off_the_fused_engine_on_gpu(tmp_path, path):
+    import __graft_entry__ as entry
+    entry.build()
+    _run_dockE3_unfused(tmp_path, None, torch.device("cuda:0"), path)
 
 
 @pytest.mark.gpu

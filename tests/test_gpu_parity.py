@@ -320,7 +320,7 @@ def test_global_docking_model_forward_and_docker_dock_volumes(dev):
     recf, ligf = torch.rand(L, L, L, generator=g), torch.rand(L, L, L, generator=g)
     dk = Docker(model, box_size=L, max_conf=K, rotations=R, device=dev)
     fused = dk.dock_volumes([rec], [lig], recf, ligf, batch_size=4, write=False)
-    entries = dk._dock_volumes_multires([rec[0]], [lig[0]], recf, ligf, 4, np.arange(9))
+    entries = dk._search_unfused("ops", [rec[0]], recf, np.arange(9), 4, dk._rotated_ligand([lig[0]], ligf), W)
     from deeplocalproteindocking_amd.engine import DeviceTopList
     generic = DeviceTopList.to_top_list(entries, 2 * L)
     scale = float(Vo.abs().max())

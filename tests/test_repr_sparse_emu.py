@@ -53,3 +53,7 @@ def test_plugin_outputs_with_maps_emulated(emu):
 
 def test_plugin_outputs_with_maps_over_two_z_tiles_emulated(emu):
     rs.check_plugin(emu, "cpu", 21, ("cuboid_xyz",))
+
+
+def test_outputs_with_maps_holds_for_the_entering_thread_only_emulated(emu):
+    rs.check_outputs_with_maps_is_per_thread(emu, "cpu", 13)
