@@ -162,8 +162,12 @@ class Docker:
     def __init__(self, docking_model, angle_inc=15.0, box_size=80, resolution=1.25, max_conf=1000,
                  randomize_rot=False, rotations=None, device="cuda", coords_backend=None,
                  rank=0, world_size=1, process_group=None, lib=None, launch_batch=None, rotation_center=None,
-                 conventions=None, rotation_seed=None, collectives_with_one_rank=False):
+                 conventions=None, rotation_seed=None, collectives_with_one_rank=False, exclusion=0):
         self.docking_model = docking_model
+        # Exclusion radius of the search in voxels (BUILD-DEFINED, include/dlpd.h dlpd_topk_suppress; 0 = the reference, which
+        # clears one voxel per pick, Docker.py:98): a rotation contributes only the voxels that nothing within `exclusion`
+        # voxels (cyclic, Chebyshev) beats.  Settable between searches; dockSE3, dockE3, dock_volumes and update_top honour it.
+        self.exclusion = int(exclusion)
         self.log = None
 
         self.box_size = box_size
@@ -329,6 +333,7 @@ class Docker:
         elif len(self.top_list) == 0:
             self._top.reset()                      # caller cleared top_list: a new pair starts
         Vc = V.contiguous()
+        self._top.exclusion = int(self.exclusion)  # (> 0: the picks of suppress_r(V); V itself loses the picked voxels only)
         _, idx = self._top.select(Vc.reshape(1, -1), 1)
         self._top.merge(torch.tensor([rotation_index], dtype=torch.int32, device=V.device), 1)
         Vc.view(-1)[idx[0].long()] = 0.0           # Docker.py:98, V is mutated in place
@@ -1131,6 +1136,7 @@ class Docker:
                 Lc = Lc if eng is not None else None
         if eng is not None:
             self.path, self.engine = ("embedded" if Lc else "fused"), eng
+            eng.exclusion = int(self.exclusion)          # (read by the reset_top() that starts the search)
         else:
             self.path = "ops" if self._ops_path_ok(rec, params) else "call"
         self.engine_box = Lc
@@ -1188,7 +1194,7 @@ class Docker:
         rf = None
         if receptor_forbidden is not None:
             rf = torch.as_tensor(receptor_forbidden, dtype=torch.float32).reshape(1, 1, L, L, L).to(dev)
-        top = DeviceTopList(self.max_conf, nbatch, dev, self._library())
+        top = DeviceTopList(self.max_conf, nbatch, dev, self._library(), exclusion=int(self.exclusion))
         top.reset()
         with torch.no_grad():
             for beg in range(0, len(ids), nbatch):

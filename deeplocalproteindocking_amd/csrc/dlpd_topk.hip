@@ -576,3 +576,6 @@ int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int*
 
 // every residue contact of the posed complex, for fnonnat: shares the predicate of dlpd_evaluate.h
 #include "dlpd_contacts.h"
+
+// exclusion radius of the search (build-defined): local-minimum suppression of V and of K3's candidate lists
+#include "dlpd_suppress.h"

@@ -34,9 +34,13 @@ class DeviceTopList:
     """Device-resident running top list: the state Docker.update_top keeps in ``self.top_list``
     (Docker.py:100-105), plus the per-rotation pick buffers (Docker.py:89-98)."""
 
-    def __init__(self, K, batch, device, lib):
+    def __init__(self, K, batch, device, lib, exclusion=0):
         self.K, self.batch, self.device, self.lib = int(K), int(batch), torch.device(device), lib
         dev = self.device
+        # exclusion radius in voxels (include/dlpd.h, dlpd_topk_suppress; build-defined, 0 = the reference): settable between
+        # selects; Vs, the suppressed copy of a batch's scores, is made at the first select that needs it
+        self.exclusion = exclusion
+        self._Vs = None
         self.cand_score = torch.empty(batch, self.K, dtype=torch.float32, device=dev)
         self.cand_idx = torch.empty(batch, self.K, dtype=torch.int32, device=dev)
         self.ws = torch.empty(lib.call("dlpd_topk_workspace_bytes", batch, self.K), dtype=torch.uint8, device=dev)
@@ -66,8 +70,26 @@ class DeviceTopList:
         exactly what ``merge()`` needs and NOT the reference's full K picks (Docker.py:89-98); rotations without a valid
         list (list not yet full, tau >= 0, overflow) get the full radix select.  A cset is SINGLE-USE: the select
         consumes and resets its counters, so it must be refilled by the scoring kernel before the next select.  Callers
-        that want the reference's K picks per rotation pass ``cset=None``."""
+        that want the reference's K picks per rotation pass ``cset=None``.
+
+        With ``exclusion`` r > 0 the picks are those of suppress_r(V) (include/dlpd.h): V is a batch of cubes, its
+        local-minimum copy Vs is what the radix select reads, and the complete candidate lists are thinned in place."""
         nvox = V[0].numel()
+        r = int(self.exclusion)
+        if r < 0:
+            raise RuntimeError("dlpd: exclusion radius %r (0 = none, the reference; 1..4 voxels)" % (self.exclusion,))
+        if r > 0:
+            n = int(round(nvox ** (1.0 / 3.0)))
+            if n * n * n != nvox:
+                raise RuntimeError("dlpd: an exclusion radius needs cubic score volumes, got %d voxels per rotation" % nvox)
+            if self._Vs is None or self._Vs.shape[1] != nvox:
+                self._Vs = torch.empty(self.batch, nvox, dtype=torch.float32, device=self.device)
+            st = _stream(self.device)
+            cc, cap = (_ptr(cset["count"]), cset["cap"]) if cset is not None else (0, 0)
+            self.lib.call("dlpd_topk_suppress", _ptr(V), _ptr(self._Vs), nb, n, r, cc, cap, st)
+            if cset is not None:
+                self.lib.call("dlpd_topk_suppress_cand", _ptr(V), nb, n, r, _ptr(cset["keys"]), cc, cap, st)
+            V = self._Vs
         if cset is None:
             self.lib.call("dlpd_topk_select", _ptr(V), nb, nvox, self.K, _ptr(self.cand_score), _ptr(self.cand_idx),
                           _ptr(self.ws), _stream(self.device))
@@ -162,7 +184,7 @@ class DockingEngine:
                  orient=True, quads=True, prefilter=True, packed_receptor=True,
                  rotation_scale=1.0, coarse_rotation_scale=None, rotation_axis_order="xyz", clip_mode="output",
                  rotation_transpose=False, keep_receptor_spectrum=False, k1_form=0, sparse_k1=None,
-                 k1_chunk_major=None):
+                 k1_chunk_major=None, exclusion=0):
         """coarse_channels > 0: the reference's two-resolution layout -- C channels at L^3 plus
         ``coarse_channels`` at (L/2)^3 (ProteinRepresentationModels.py:72-76); W1 is (H, C+coarse).
         extent < L: the volumes are extent^3 boxes in the corner of the L^3 ones (a box size without a compiled plan
@@ -197,6 +219,9 @@ class DockingEngine:
         self.threshold = float(threshold_clash)
         self.K = int(max_conf)
         self.batch = int(batch)
+        # exclusion radius of the search in voxels (include/dlpd.h, dlpd_topk_suppress; build-defined, 0 = the reference's
+        # list): read at reset_top(), so a live engine serves searches with different radii
+        self.exclusion = int(exclusion)
         dev = self.device
         f32 = torch.float32
         self.C1 = int(coarse_channels)
@@ -309,6 +334,7 @@ class DockingEngine:
                 "k1_form": {0: "library default", 1: "phased", 2: "role-split"}[self.k1_form],
                 "k3_form": {0: "library default (role-split where compiled)", 1: "channel-owning", 2: "role-split"}[self.k3_form],
                 "k3_unfused": bool(self.fine_unfused), "topk_candidate_lists": bool(self.prefilter),
+                "exclusion": int(self.exclusion),
                 "k2_packed_receptor": {"fine": fine.recP is not None, "coarse": bool(c and c.recP is not None)},
                 "embedded_extent": self.extent or None,
                 "k1_occupancy_maps": {"fine": fine.sparse, "coarse": bool(c and c.sparse),
@@ -633,6 +659,7 @@ class DockingEngine:
 
     def reset_top(self):
         self.finish()                                   # nothing of the previous pair still in flight
+        self.top.exclusion = int(self.exclusion)        # (the radius of THIS search: fixed until the next reset)
         self.top.reset()
 
     def select_batch(self, V, nb, cset=None):

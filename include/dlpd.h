@@ -532,6 +532,27 @@ int dlpd_topk_merge(const float* cand_score, const int* cand_idx, const int* rot
 int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int* rot_ids, int nb, int K,
                         void* glist, void* tau_out, void* stream);
 
+/* Exclusion radius of the search.  BUILD-DEFINED, both entries: the reference clears ONE voxel per pick
+ * (Docker.py:98) and has no counterpart; r = 0 -- neither call -- is the reference.  On the cubic grid of side n with flat
+ * index (x n + y) n + z and an integer radius r >= 1: u BEATS v iff V[u] < V[v], or V[u] == V[v] and flat(u) < flat(v);
+ * B_r(v) is the cyclic Chebyshev ball {(v + d) mod n : d in [-r, r]^3}.  suppress_r(V)[v] is V[v] itself where V[v] < 0 is
+ * false (zeros, -0.0 and positives keep their bits), V[v] where V[v] < 0 and no other voxel of B_r(v) beats v, and +0.0 --
+ * what a pick of the reference leaves in the voxel it took -- everywhere else.  The list of a search with exclusion r is
+ * Docker.update_top run on suppress_r(V) for every rotation: pick order, the zero-fill behaviour and the merge key keep their
+ * definitions, and no two negative entries of one rotation lie within r voxels of each other on the wrapped grid.  NaN scores
+ * are outside the contract, as for the select.
+ * dlpd_topk_suppress: Vs (nb, n^3) = suppress_r(V), never in place.  cand_count (null: every rotation; else the 2 nb words of
+ *   dlpd_topk_select_cand): the rows of rotations whose candidate list is complete (flag clear, count <= cap) are NOT written
+ *   -- the select reads Vs only for the rotations it radix-selects.
+ * dlpd_topk_suppress_cand: every complete list loses the candidates that some voxel of their ball beats in V (whatever beats
+ *   a candidate scores below it, so V is all the test needs); survivors keep their order, cand_count[b] is lowered;
+ *   incomplete lists and the flags are left alone.  cap in [64, 8192].
+ * Order within a launch: dlpd_topk_suppress (flags given), dlpd_topk_suppress_cand, dlpd_topk_select_cand on Vs.
+ * r < 1, r > 4, 2 r + 1 > n, nb <= 0, a null pointer, V == Vs: DLPD_ERR_ARG; n^3 >= 2^31: DLPD_ERR_UNSUPPORTED; on an error
+ * nothing is launched. */
+int dlpd_topk_suppress(const float* V, float* Vs, int nb, int n, int r, const void* cand_count, int cap, void* stream);
+int dlpd_topk_suppress_cand(const float* V, int nb, int n, int r, void* cand_keys, void* cand_count, int cap, void* stream);
+
 /* Pose clustering of a finished list.  BUILD-DEFINED, all four entries: the reference has no counterpart and no call site
  * (Docker.cluster is this build's own step after the search).  A rigid pose p = (R_p, t_p) of one ligand is handed over as
  * its embedding e_p, 12 floats (ops.pose_embedding): the RMSD between two poses over the ligand's (weighted) atoms is the

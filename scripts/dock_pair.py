@@ -19,6 +19,10 @@ without the benchmark table: representation -> exhaustive rotation x translation
                                            # the unbound structures) -> <out>.eval.txt, one line per pose of the .dat, and a
                                            # summary; likewise <out>.refined.eval.txt / .minimized.eval.txt / .clustered.eval.txt
                                            # for the lists of the steps that ran
+        [--exclusion R]                    # exclusion radius of the search in voxels (0..4, default 0 = the reference's list): a
+                                           # rotation contributes only the voxels that nothing within R voxels beats
+                                           # (Docker(exclusion=R), build-defined), so the list holds distinct minima instead of
+                                           # the neighbours of a few; every later step takes that list as it is
         [--decoys DIR[:NEAR[:FAR]]]        # with --native: write a training set for this target under DIR in the layout
                                            # Dataset.get_dataset_stream reads (Dataset.DecoySet): NEAR poses round the native one
                                            # (default 10) and the first FAR poses (default 10) of the list the run ends with -- the
@@ -41,6 +45,21 @@ def parse_cluster(spec):
     """RADIUS[:KEEP] -> (radius in Angstrom, keep or None)"""
     part = spec.split(":")
     return float(part[0]), (int(part[1]) if len(part) > 1 and part[1] else None)
+
+
+def parse_exclusion(spec):
+    """R -> the exclusion radius in voxels, 0 (none) .. 4"""
+    r = int(spec)
+    if not 0 <= r <= 4:
+        raise ValueError("--exclusion takes 0 (none, the reference's list) .. 4 voxels, got %r" % (spec,))
+    return r
+
+
+def search(docker, receptor, ligand, group, batch_size, prepared=None, exclusion=0):
+    """The search step: ``Docker.dockSE3`` / ``dockE3`` with the exclusion radius of ``--exclusion`` -> the top list."""
+    docker.exclusion = parse_exclusion(exclusion)
+    (docker.dockSE3 if group == "SE3" else docker.dockE3)(receptor, ligand, batch_size, prepared=prepared)
+    return docker.top_list
 
 
 def cluster_and_write(docker, prepared, out, radius, keep=None, poses=None, rank=0):
@@ -132,6 +151,7 @@ def main():
     ap.add_argument("--cluster", default=None, metavar="RADIUS[:KEEP]")
     ap.add_argument("--native", default=None, nargs=2, metavar=("BOUND_REC.pdb", "BOUND_LIG.pdb"))
     ap.add_argument("--decoys", default=None, metavar="DIR[:NEAR[:FAR]]")
+    ap.add_argument("--exclusion", default=0, type=parse_exclusion, metavar="R")
     args = ap.parse_args()
     if args.decoys is not None and args.native is None:
         ap.error("--decoys needs --native (the decoys are labelled against the native complex)")
@@ -170,7 +190,7 @@ def main():
         ap.error("--cluster needs -group SE3 (the poses move the prepared ligand's atoms)")
     with torch.no_grad():
         prepared = docker.prepare(args.receptor, args.ligand, "SE3") if (refine or args.minimize is not None or args.cluster is not None) else None
-        (docker.dockSE3 if args.group == "SE3" else docker.dockE3)(args.receptor, args.ligand, args.batch_size, prepared=prepared)
+        search(docker, args.receptor, args.ligand, args.group, args.batch_size, prepared=prepared, exclusion=args.exclusion)
     docker.cleanup()
     if rank == 0:
         print("wrote", args.out, "(%d poses, best score %f)" % (len(docker.top_list), docker.top_list[0][4]))
