@@ -138,6 +138,7 @@ class PreparedPair(object):
         self.group, self.ureceptor, self.uligand, self.slot = group, ureceptor, uligand, slot
         self.receptor = self.receptor_volumes = self.receptor_forbidden = self.ligand_volumes = None
         self.ligand_atoms = None           # (coords, num_atoms_of_type, offsets) on the device, origin-centred
+        self.receptor_shift = self.ligand_shift = None   # the centring shifts load_batch returned: file frame + shift = origin-centred
         self.engine = None                 # fused engine with receptor (and, SE3, ligand) already set; None: other paths
         self.ready = None                  # torch.cuda.Event recorded on the producer's stream
         self.seconds = 0.0                 # host time of the preparation
@@ -162,12 +163,19 @@ class Docker:
     def __init__(self, docking_model, angle_inc=15.0, box_size=80, resolution=1.25, max_conf=1000,
                  randomize_rot=False, rotations=None, device="cuda", coords_backend=None,
                  rank=0, world_size=1, process_group=None, lib=None, launch_batch=None, rotation_center=None,
-                 conventions=None, rotation_seed=None, collectives_with_one_rank=False, exclusion=0):
+                 conventions=None, rotation_seed=None, collectives_with_one_rank=False, exclusion=0,
+                 restraints=None, restraints_needed=None):
         self.docking_model = docking_model
         # Exclusion radius of the search in voxels (BUILD-DEFINED, include/dlpd.h dlpd_topk_suppress; 0 = the reference, which
         # clears one voxel per pick, Docker.py:98): a rotation contributes only the voxels that nothing within `exclusion`
         # voxels (cyclic, Chebyshev) beats.  Settable between searches; dockSE3, dockE3, dock_volumes and update_top honour it.
         self.exclusion = int(exclusion)
+        # Distance restraints of the search (BUILD-DEFINED, include/dlpd.h dlpd_topk_restrain; None = the reference): a list of
+        # Utils.Restraints.Restraint in the search frame (restraints_from_selections makes them from PDB selections), of which
+        # a pose must satisfy restraints_needed (None: all).  Settable between searches; dockSE3, dockE3, dock_volumes and
+        # update_top honour them.  Every rank builds the same table from the full rotation set: no collective.
+        self.restraints = restraints
+        self.restraints_needed = restraints_needed
         self.log = None
 
         self.box_size = box_size
@@ -322,6 +330,51 @@ class Docker:
             self._lib = get_lib()
         return self._lib
 
+    def restraint_table(self):
+        """The integer table of ``self.restraints`` over this Docker's whole rotation set (None without restraints); built once
+        per (restraints, restraints_needed) object pair."""
+        if not self.restraints:
+            return None
+        key = (tuple((r.receptor_point.tobytes(), r.ligand_point.tobytes(), r.dmax, r.dmin) for r in self.restraints),
+               self.restraints_needed, float(self.resolution))
+        if getattr(self, "_rst_table", (None, None))[0] != key:
+            from deeplocalproteindocking_amd.Utils.Restraints import restraint_table
+            self._rst_table = (key, restraint_table(self.rot.R, self.restraints, self.resolution, self.restraints_needed))
+        return self._rst_table[1]
+
+    def restraints_from_selections(self, prepared, selections):
+        """[(receptor selection, ligand selection, dmax[, dmin]), ...] -- "CHAIN:RESNUM[:ATOM]" in the two PDB files of
+        ``prepared`` (Utils.Restraints.select_point) -> [Restraint] in the search frame: the receptor point becomes
+        randR (x + shift), the ligand point x + shift, with the centring shifts the pair was prepared with."""
+        from deeplocalproteindocking_amd.Utils.Restraints import Restraint, select_point
+        rsh = np.asarray(torch.as_tensor(prepared.receptor_shift).detach().cpu(), dtype=np.float64).reshape(3)
+        lsh = np.asarray(torch.as_tensor(prepared.ligand_shift).detach().cpu(), dtype=np.float64).reshape(3)
+        randR = self.randR.squeeze().to(torch.float64).cpu().numpy() if self.randomize_rot else np.eye(3)
+        out = []
+        for sel in selections:
+            rec_sel, lig_sel, dmax = sel[0], sel[1], sel[2]
+            dmin = sel[3] if len(sel) > 3 else 0.0
+            b = randR @ (select_point(prepared.ureceptor, rec_sel) + rsh)
+            a = select_point(prepared.uligand, lig_sel) + lsh
+            out.append(Restraint(b, a, dmax, dmin))
+        return out
+
+    def restraint_report(self, poses=None):
+        """Number of ``self.restraints`` each pose satisfies -> int array (default: ``self.top_list``; any list form of
+        ``_pose_arrays``; the fractional translations of a ``refined_list`` are taken as they stand).  Host side.  Entries of a
+        ``top_list`` go by their rotation index and the search's own integer test; other forms by their own rotation matrix."""
+        from deeplocalproteindocking_amd.Utils.Restraints import restraint_table, satisfied
+        poses = self.top_list if poses is None else poses
+        if not self.restraints:
+            raise RuntimeError("dlpd: restraint_report without restraints")
+        if len(poses) == 0:
+            return np.zeros(0, dtype=np.int64)
+        R, t, own, _ = self._pose_arrays(poses)
+        if all(len(e) == 5 for e in poses):
+            return satisfied(self.restraint_table(), np.array([int(e[0]) for e in poses]), np.array(own, dtype=np.int64).reshape(-1, 3))
+        tab = restraint_table(R, self.restraints, self.resolution, self.restraints_needed)
+        return satisfied(tab, np.arange(len(poses)), t)
+
     def update_top(self, V, rotation_index):
         """V (N,N,N) float32 device tensor.  Same observable behaviour as Docker.py:86-105: the
         max_conf picks are appended to ``self.top_list`` (stable sort, truncate) and the picked
@@ -334,8 +387,12 @@ class Docker:
             self._top.reset()                      # caller cleared top_list: a new pair starts
         Vc = V.contiguous()
         self._top.exclusion = int(self.exclusion)  # (> 0: the picks of suppress_r(V); V itself loses the picked voxels only)
-        _, idx = self._top.select(Vc.reshape(1, -1), 1)
-        self._top.merge(torch.tensor([rotation_index], dtype=torch.int32, device=V.device), 1)
+        tab = self.restraint_table()
+        if tab is not self._top.restraints:
+            self._top.set_restraints(tab)
+        rid = torch.tensor([rotation_index], dtype=torch.int32, device=V.device)
+        _, idx = self._top.select(Vc.reshape(1, -1), 1, None, rid)
+        self._top.merge(rid, 1)
         Vc.view(-1)[idx[0].long()] = 0.0           # Docker.py:98, V is mutated in place
         if Vc.data_ptr() != V.data_ptr():
             V.copy_(Vc)
@@ -1137,6 +1194,7 @@ class Docker:
         if eng is not None:
             self.path, self.engine = ("embedded" if Lc else "fused"), eng
             eng.exclusion = int(self.exclusion)          # (read by the reset_top() that starts the search)
+            eng.restraints = self.restraint_table()
         else:
             self.path = "ops" if self._ops_path_ok(rec, params) else "call"
         self.engine_box = Lc
@@ -1195,6 +1253,7 @@ class Docker:
         if receptor_forbidden is not None:
             rf = torch.as_tensor(receptor_forbidden, dtype=torch.float32).reshape(1, 1, L, L, L).to(dev)
         top = DeviceTopList(self.max_conf, nbatch, dev, self._library(), exclusion=int(self.exclusion))
+        top.set_restraints(self.restraint_table())
         top.reset()
         with torch.no_grad():
             for beg in range(0, len(ids), nbatch):
@@ -1215,8 +1274,9 @@ class Docker:
                     if norm is not None:
                         V = torch.lt(norm, model.threshold_clash).to(dtype=torch.float32) * V
                     V = V.contiguous()
-                top.select(V.reshape(nb, -1), nb)
-                top.merge(torch.as_tensor(bid, dtype=torch.int32).to(dev), nb)
+                bid_dev = torch.as_tensor(bid, dtype=torch.int32).to(dev)
+                top.select(V.reshape(nb, -1), nb, None, bid_dev)
+                top.merge(bid_dev, nb)
         return top.entries()
 
     def _gather(self, entries):
@@ -1279,6 +1339,7 @@ class Docker:
         with (torch.cuda.stream(stream) if on_stream else contextlib.nullcontext()), torch.no_grad():
             rcoords, rnat, roff, rT, rnatoms = self.load_batch([ureceptor], bbox_center=False)
             lcoords, lnat, loff, lT, lnatoms = self.load_batch([uligand], bbox_center=False)
+            p.receptor_shift, p.ligand_shift = rT, lT
             if self.randomize_rot:
                 rcoords = be.rotate(rcoords, self.randR, rnatoms)
             rcoords = be.translate(rcoords, self.box_center, rnatoms)

@@ -122,6 +122,8 @@ SIGNATURES = {
     "dlpd_topk_merge": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "dlpd_topk_suppress": (_i, [_p, _p, _i, _i, _i, _p, _i, _p]),
     "dlpd_topk_suppress_cand": (_i, [_p, _i, _i, _i, _p, _p, _i, _p]),
+    "dlpd_topk_restrain": (_i, [_p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _i, _p]),
+    "dlpd_topk_restrain_cand": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i, _p]),
     "dlpd_pose_rmsd": (_i, [_p, _p, _p, _i, _i, _p]),
     "dlpd_pose_within": (_i, [_p, _i, _f, _p, _p]),
     "dlpd_pose_cluster_ws": (_sz, [_i]),

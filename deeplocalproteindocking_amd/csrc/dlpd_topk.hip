@@ -579,3 +579,6 @@ int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int*
 
 // exclusion radius of the search (build-defined): local-minimum suppression of V and of K3's candidate lists
 #include "dlpd_suppress.h"
+
+// distance restraints of the search (build-defined): allowed-region masking of V, thinning and rebuilding of K3's candidate lists
+#include "dlpd_restrain.h"

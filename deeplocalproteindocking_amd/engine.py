@@ -41,6 +41,9 @@ class DeviceTopList:
         # selects; Vs, the suppressed copy of a batch's scores, is made at the first select that needs it
         self.exclusion = exclusion
         self._Vs = None
+        # distance restraints (include/dlpd.h, dlpd_topk_restrain; build-defined, None = the reference): set_restraints
+        self.restraints = None
+        self._rst = None
         self.cand_score = torch.empty(batch, self.K, dtype=torch.float32, device=dev)
         self.cand_idx = torch.empty(batch, self.K, dtype=torch.int32, device=dev)
         self.ws = torch.empty(lib.call("dlpd_topk_workspace_bytes", batch, self.K), dtype=torch.uint8, device=dev)
@@ -60,7 +63,20 @@ class DeviceTopList:
         self.lib.call("dlpd_topk_glist_reset", _ptr(self.glist), self.K, _stream(self.device))
         self.tau.zero_()
 
-    def select(self, V, nb, cset=None):
+    # Overflowed candidate lists are rebuilt from the restraints' bounding cubes while those hold at most this many voxels
+    # (one block per rotation walks them): 65^3, the largest cube at which a rebuilt launch was measured and found no slower
+    # than the full path on the same rotations (EXPERIMENTS.md RESTRAINTS); above it, and with None, only thinning runs
+    REBUILD_LIMIT = 65 ** 3
+
+    def set_restraints(self, table):
+        """table: a ``Utils.Restraints.RestraintTable`` for the whole rotation set (or None: no restraints, exactly the calls
+        of a free search).  Uploaded once; settable between searches."""
+        self.restraints = table
+        self._rst = None
+        if table is not None:
+            self._rst = (torch.from_numpy(table.centres.copy()).to(self.device), torch.from_numpy(table.bounds.copy()).to(self.device))
+
+    def select(self, V, nb, cset=None, rot_ids=None):
         """V (nb, nvox) contiguous -> (scores, flat indices) (nb, K) in the reference's pick order.
         cset: the candidate set the scoring kernel filled for exactly these nb rotations (or None).
 
@@ -73,22 +89,44 @@ class DeviceTopList:
         that want the reference's K picks per rotation pass ``cset=None``.
 
         With ``exclusion`` r > 0 the picks are those of suppress_r(V) (include/dlpd.h): V is a batch of cubes, its
-        local-minimum copy Vs is what the radix select reads, and the complete candidate lists are thinned in place."""
+        local-minimum copy Vs is what the radix select reads, and the complete candidate lists are thinned in place.
+
+        With restraints set (``set_restraints``) the picks are those of restrain(V): ``rot_ids`` -- the batch's global rotation
+        indices, int32 on the device, what ``merge`` gets -- index the table; the complete candidate lists lose what is not
+        allowed, the overflowed ones are rebuilt from the allowed region, and Vs is masked for the rest.  Both: the
+        intersection, a local minimum of the unrestricted V that is allowed."""
         nvox = V[0].numel()
         r = int(self.exclusion)
+        tab = self.restraints
         if r < 0:
             raise RuntimeError("dlpd: exclusion radius %r (0 = none, the reference; 1..4 voxels)" % (self.exclusion,))
-        if r > 0:
+        if r > 0 or tab is not None:
             n = int(round(nvox ** (1.0 / 3.0)))
             if n * n * n != nvox:
-                raise RuntimeError("dlpd: an exclusion radius needs cubic score volumes, got %d voxels per rotation" % nvox)
+                raise RuntimeError("dlpd: %s needs cubic score volumes, got %d voxels per rotation" %
+                                   ("an exclusion radius" if r > 0 else "a restraint set", nvox))
+            if tab is not None and rot_ids is None:
+                raise RuntimeError("dlpd: a restrained select needs rot_ids, the batch's global rotation indices")
+            if tab is not None and n % 2:
+                raise RuntimeError("dlpd: a restraint set needs score volumes of even side, got %d" % n)
             if self._Vs is None or self._Vs.shape[1] != nvox:
                 self._Vs = torch.empty(self.batch, nvox, dtype=torch.float32, device=self.device)
             st = _stream(self.device)
             cc, cap = (_ptr(cset["count"]), cset["cap"]) if cset is not None else (0, 0)
-            self.lib.call("dlpd_topk_suppress", _ptr(V), _ptr(self._Vs), nb, n, r, cc, cap, st)
-            if cset is not None:
-                self.lib.call("dlpd_topk_suppress_cand", _ptr(V), nb, n, r, _ptr(cset["keys"]), cc, cap, st)
+            src = V
+            if tab is not None:
+                rst = (_ptr(rot_ids), _ptr(self._rst[0]), _ptr(self._rst[1]), tab.J, tab.need)
+                if cset is not None:
+                    rebuild = self.REBUILD_LIMIT is not None and tab.cube_volume() <= self.REBUILD_LIMIT
+                    self.lib.call("dlpd_topk_restrain_cand", _ptr(V), nb, n, *rst, _ptr(self.tau) if rebuild else 0,
+                                  _ptr(cset["keys"]), cc, cap, st)
+            if r > 0:
+                self.lib.call("dlpd_topk_suppress", _ptr(V), _ptr(self._Vs), nb, n, r, cc, cap, st)
+                if cset is not None:
+                    self.lib.call("dlpd_topk_suppress_cand", _ptr(V), nb, n, r, _ptr(cset["keys"]), cc, cap, st)
+                src = self._Vs
+            if tab is not None:
+                self.lib.call("dlpd_topk_restrain", _ptr(src), _ptr(self._Vs), nb, n, *rst, cc, cap, st)
             V = self._Vs
         if cset is None:
             self.lib.call("dlpd_topk_select", _ptr(V), nb, nvox, self.K, _ptr(self.cand_score), _ptr(self.cand_idx),
@@ -184,7 +222,7 @@ class DockingEngine:
                  orient=True, quads=True, prefilter=True, packed_receptor=True,
                  rotation_scale=1.0, coarse_rotation_scale=None, rotation_axis_order="xyz", clip_mode="output",
                  rotation_transpose=False, keep_receptor_spectrum=False, k1_form=0, sparse_k1=None,
-                 k1_chunk_major=None, exclusion=0):
+                 k1_chunk_major=None, exclusion=0, restraints=None):
         """coarse_channels > 0: the reference's two-resolution layout -- C channels at L^3 plus
         ``coarse_channels`` at (L/2)^3 (ProteinRepresentationModels.py:72-76); W1 is (H, C+coarse).
         extent < L: the volumes are extent^3 boxes in the corner of the L^3 ones (a box size without a compiled plan
@@ -222,6 +260,9 @@ class DockingEngine:
         # exclusion radius of the search in voxels (include/dlpd.h, dlpd_topk_suppress; build-defined, 0 = the reference's
         # list): read at reset_top(), so a live engine serves searches with different radii
         self.exclusion = int(exclusion)
+        # distance restraints of the search (Utils.Restraints.RestraintTable over the whole rotation set, or None; build-defined):
+        # read at reset_top(), as the radius is
+        self.restraints = restraints
         dev = self.device
         f32 = torch.float32
         self.C1 = int(coarse_channels)
@@ -335,6 +376,7 @@ class DockingEngine:
                 "k3_form": {0: "library default (role-split where compiled)", 1: "channel-owning", 2: "role-split"}[self.k3_form],
                 "k3_unfused": bool(self.fine_unfused), "topk_candidate_lists": bool(self.prefilter),
                 "exclusion": int(self.exclusion),
+                "restraints": None if self.restraints is None else (self.restraints.J, self.restraints.need),
                 "k2_packed_receptor": {"fine": fine.recP is not None, "coarse": bool(c and c.recP is not None)},
                 "embedded_extent": self.extent or None,
                 "k1_occupancy_maps": {"fine": fine.sparse, "coarse": bool(c and c.sparse),
@@ -660,15 +702,18 @@ class DockingEngine:
     def reset_top(self):
         self.finish()                                   # nothing of the previous pair still in flight
         self.top.exclusion = int(self.exclusion)        # (the radius of THIS search: fixed until the next reset)
+        if self.restraints is not self.top.restraints:
+            self.top.set_restraints(self.restraints)    # (and its restraint set)
         self.top.reset()
 
-    def select_batch(self, V, nb, cset=None):
+    def select_batch(self, V, nb, cset=None, rot_ids=None):
         """Per-rotation picks of Docker.update_top (Docker.py:89-98) for V (nb, N^3).  cset: the candidate set the
         scoring kernel filled for this batch -- then the rows hold only the picks that can still enter the running list
-        (+inf padded) and the cset is consumed; see ``DeviceTopList.select``."""
+        (+inf padded) and the cset is consumed; see ``DeviceTopList.select``.  rot_ids: the batch's rotation indices as
+        ``merge_batch`` gets them -- needed by a restrained search only."""
         if self.window is not None:
             V = self.gather_window(V, nb)
-        return self.top.select(V.reshape(nb, -1), nb, cset)
+        return self.top.select(V.reshape(nb, -1), nb, cset, rot_ids)
 
     def gather_window(self, V, nb):
         """(nb, N^3) scores of this engine's grid -> (nb, (2 extent)^3): the reference's grid of the embedded box."""
@@ -701,7 +746,7 @@ class DockingEngine:
         if self._side is None:                          # emulated library (tests): same calls, one stream
             V = self.score_batch(R, mark=mark, volumes=volumes, transposed=transposed, quads=quads,
                                  cset=self._csets[0], occupancy=occupancy)
-            self.select_batch(V, nb, self._cset_used)
+            self.select_batch(V, nb, self._cset_used, rot_ids)
             self.merge_batch(rot_ids, nb)
             return
         k = self._k
@@ -735,7 +780,7 @@ class DockingEngine:
         with torch.cuda.stream(self._side):
             self._side.wait_event(ready)
             self._side.wait_event(gate)
-            self.select_batch(V, nb, cset)
+            self.select_batch(V, nb, cset, rot_ids)
             self.merge_batch(rot_ids, nb)
             done = torch.cuda.Event()
             done.record(self._side)

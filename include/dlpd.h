@@ -553,6 +553,45 @@ int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int*
 int dlpd_topk_suppress(const float* V, float* Vs, int nb, int n, int r, const void* cand_count, int cap, void* stream);
 int dlpd_topk_suppress_cand(const float* V, int nb, int n, int r, void* cand_keys, void* cand_count, int cap, void* stream);
 
+/* Search under distance restraints.  BUILD-DEFINED, both entries: the reference has no counterpart; without
+ * restraints -- neither call -- is the reference.  Poses as Docker.cluster / Docker.evaluate take them: list entry
+ * (rot, x, y, z) carries a ligand point a (Angstrom, ligand centred on the origin) to R_rot a + resolution t, t the signed
+ * translation of (x, y, z); a receptor point b is in Angstrom in the search frame (origin-centred, after randR).  Restraint
+ * j = (a_j, b_j, dmin_j, dmax_j), 0 <= dmin <= dmax < inf, is satisfied iff dmin <= |R a + res t - b| <= dmax; a set is J
+ * restraints (1..32) and a number need (1..J), and a pose is ALLOWED iff it satisfies at least `need` of them.
+ * The predicate is evaluated in integers, in units of 1/256 voxel (0.005 A at 1.25 A: the step of the test).  The host
+ * computes in float64 the centres c[rot][j] = round_half_even(256 (b_j - R_rot a_j) / resolution), int32 (nrot, J, 3),
+ * |c| <= 2^20, and lo_j = round(256 dmin / res), hi_j = round(256 dmax / res) <= 2^21, stored squared as int64: bounds =
+ * lo^2 of the J restraints, then hi^2.  For voxel v of the cubic grid of EVEN side n the signed index per axis is
+ * t = v - n if v >= n / 2 else v (Docker.signed_translation with box_size = n / 2: on an embedded box the test is on the
+ * reported pose), d^2 = sum over the axes of (256 t - c)^2 in int64, and the restraint is satisfied iff lo^2 <= d^2 <= hi^2,
+ * both ends inclusive.  A centre outside the grid is legal; the restraint is then unsatisfiable for that rotation.
+ * restrain(V)[v] is V[v] itself where V[v] < 0 is false (zeros, -0.0 and positives keep their bits) and where V[v] < 0 and v
+ * is allowed, +0.0 everywhere else.  The list of a restrained search is Docker.update_top run on restrain(V) for every
+ * rotation: every negative entry of the list is an allowed pose (zero-fill entries are outside that promise, as for the
+ * exclusion radius).  With an exclusion radius as well the result is the intersection: a voxel survives iff it is a local
+ * minimum of the UNRESTRICTED V and is allowed -- the two masks commute, and a rejected minimum still suppresses its
+ * neighbours.
+ * dlpd_topk_restrain: Vs (nb, n^3) = restrain(V); Vs == V is allowed.  rot_ids: the batch's global rotation indices, device
+ *   int32 (the tensor dlpd_topk_merge gets); they index centres.  cand_count as for dlpd_topk_suppress: the rows of rotations
+ *   whose candidate list is complete are NOT written.
+ * dlpd_topk_restrain_cand: every complete list (flag clear, count <= cap) loses the candidates that are not allowed; survivors
+ *   keep their order, cand_count[b] is lowered.  With tau (the word dlpd_topk_merge_tau publishes; null or *tau == 0: no
+ *   rebuild) every OVERFLOWED list (flag clear, count > cap) is rebuilt from the bounding cubes of the J balls, clipped to the
+ *   grid: every allowed voxel whose key is <= *tau, each once; if they are at most cap the list is complete and its count
+ *   set, else the count stays above cap.  Flagged lists and the flags are left alone.  The caller bounds the summed volume
+ *   of the cubes (one block walks them).  cap in [64, 8192].
+ * Order within a launch: dlpd_topk_restrain_cand; dlpd_topk_suppress and dlpd_topk_suppress_cand when there is a radius (they
+ * thin the rebuilt lists too); dlpd_topk_restrain (flags given; in place on Vs after a suppress, V -> Vs otherwise);
+ * dlpd_topk_select_cand on Vs.  Without candidate lists: dlpd_topk_restrain, then dlpd_topk_select on Vs.
+ * An odd n, J outside [1, 32], need outside [1, J], nb <= 0, a null required pointer, cap outside [64, 8192] (cand entry):
+ * DLPD_ERR_ARG; n^3 >= 2^31: DLPD_ERR_UNSUPPORTED; on an error nothing is launched. */
+int dlpd_topk_restrain(const float* V, float* Vs, int nb, int n, const int* rot_ids, const int* centres,
+                       const long long* bounds, int J, int need, const void* cand_count, int cap, void* stream);
+int dlpd_topk_restrain_cand(const float* V, int nb, int n, const int* rot_ids, const int* centres,
+                            const long long* bounds, int J, int need, const void* tau, void* cand_keys, void* cand_count,
+                            int cap, void* stream);
+
 /* Pose clustering of a finished list.  BUILD-DEFINED, all four entries: the reference has no counterpart and no call site
  * (Docker.cluster is this build's own step after the search).  A rigid pose p = (R_p, t_p) of one ligand is handed over as
  * its embedding e_p, 12 floats (ops.pose_embedding): the RMSD between two poses over the ligand's (weighted) atoms is the

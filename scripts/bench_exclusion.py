@@ -70,14 +70,14 @@ class FullPathCounter(object):
         self.total = 0
         top.select = self
 
-    def __call__(self, V, nb, cset=None):
+    def __call__(self, V, nb, cset=None, rot_ids=None):
         if cset is None:
             self.full += nb
         else:
             c = cset["count"]
             self.full += ((c[self.top.batch:self.top.batch + nb] != 0) | (c[:nb] > cset["cap"])).sum()
         self.total += nb
-        return self.inner(V, nb, cset)
+        return self.inner(V, nb, cset, rot_ids)
 
 
 def bench_step(args, dev):

@@ -19,6 +19,11 @@ without the benchmark table: representation -> exhaustive rotation x translation
                                            # the unbound structures) -> <out>.eval.txt, one line per pose of the .dat, and a
                                            # summary; likewise <out>.refined.eval.txt / .minimized.eval.txt / .clustered.eval.txt
                                            # for the lists of the steps that ran
+        [--restraint REC_SEL LIG_SEL DMAX[:DMIN]]...   # distance restraints of the search (build-defined): the atom selected in
+                                           # the receptor file ("CHAIN:RESNUM[:ATOM]", CA by default, * = the residue's
+                                           # centroid, _ = blank chain) lies within [DMIN, DMAX] Angstrom of the one selected
+                                           # in the ligand file; only poses that satisfy them enter the list
+        [--restraints-needed M]            # ... at least M of them (default: all)
         [--exclusion R]                    # exclusion radius of the search in voxels (0..4, default 0 = the reference's list): a
                                            # rotation contributes only the voxels that nothing within R voxels beats
                                            # (Docker(exclusion=R), build-defined), so the list holds distinct minima instead of
@@ -55,9 +60,34 @@ def parse_exclusion(spec):
     return r
 
 
-def search(docker, receptor, ligand, group, batch_size, prepared=None, exclusion=0):
-    """The search step: ``Docker.dockSE3`` / ``dockE3`` with the exclusion radius of ``--exclusion`` -> the top list."""
+def parse_restraint_distance(spec):
+    """DMAX[:DMIN] -> (dmax, dmin) in Angstrom"""
+    part = str(spec).split(":")
+    dmax, dmin = float(part[0]), (float(part[1]) if len(part) > 1 and part[1] else 0.0)
+    if not 0.0 <= dmin <= dmax < float("inf"):
+        raise ValueError("--restraint takes DMAX[:DMIN] with 0 <= DMIN <= DMAX, got %r" % (spec,))
+    return dmax, dmin
+
+
+def set_restraints(docker, prepared, restraints, needed=None):
+    """``--restraint REC_SEL LIG_SEL DMAX[:DMIN]`` (repeated) and ``--restraints-needed M`` -> ``docker.restraints``: the
+    selections are looked up in the pair's two PDB files and mapped into the search frame (``restraints_from_selections``)."""
+    if not restraints:
+        docker.restraints, docker.restraints_needed = None, None
+        return None
+    sel = [(r[0], r[1]) + parse_restraint_distance(r[2]) for r in restraints]
+    if needed is not None and not 1 <= int(needed) <= len(sel):
+        raise ValueError("--restraints-needed takes 1 .. %d (the number of --restraint), got %r" % (len(sel), needed))
+    docker.restraints = docker.restraints_from_selections(prepared, sel)
+    docker.restraints_needed = None if needed is None else int(needed)
+    return docker.restraints
+
+
+def search(docker, receptor, ligand, group, batch_size, prepared=None, exclusion=0, restraints=None, restraints_needed=None):
+    """The search step: ``Docker.dockSE3`` / ``dockE3`` with the exclusion radius of ``--exclusion`` and the restraints of
+    ``--restraint`` (they need ``prepared``: its centring shifts place the selections) -> the top list."""
     docker.exclusion = parse_exclusion(exclusion)
+    set_restraints(docker, prepared, restraints, restraints_needed)
     (docker.dockSE3 if group == "SE3" else docker.dockE3)(receptor, ligand, batch_size, prepared=prepared)
     return docker.top_list
 
@@ -152,7 +182,11 @@ def main():
     ap.add_argument("--native", default=None, nargs=2, metavar=("BOUND_REC.pdb", "BOUND_LIG.pdb"))
     ap.add_argument("--decoys", default=None, metavar="DIR[:NEAR[:FAR]]")
     ap.add_argument("--exclusion", default=0, type=parse_exclusion, metavar="R")
+    ap.add_argument("--restraint", default=[], action="append", nargs=3, metavar=("REC_SEL", "LIG_SEL", "DMAX[:DMIN]"))
+    ap.add_argument("--restraints-needed", default=None, type=int, metavar="M")
     args = ap.parse_args()
+    if args.restraints_needed is not None and not args.restraint:
+        ap.error("--restraints-needed needs --restraint")
     if args.decoys is not None and args.native is None:
         ap.error("--decoys needs --native (the decoys are labelled against the native complex)")
     entry.build()
@@ -190,10 +224,14 @@ def main():
         ap.error("--cluster needs -group SE3 (the poses move the prepared ligand's atoms)")
     with torch.no_grad():
         prepared = docker.prepare(args.receptor, args.ligand, "SE3") if (refine or args.minimize is not None or args.cluster is not None) else None
-        search(docker, args.receptor, args.ligand, args.group, args.batch_size, prepared=prepared, exclusion=args.exclusion)
+        if args.restraint and prepared is None:
+            prepared = docker.prepare(args.receptor, args.ligand, args.group)
+        search(docker, args.receptor, args.ligand, args.group, args.batch_size, prepared=prepared, exclusion=args.exclusion,
+               restraints=args.restraint, restraints_needed=args.restraints_needed)
     docker.cleanup()
     if rank == 0:
-        print("wrote", args.out, "(%d poses, best score %f)" % (len(docker.top_list), docker.top_list[0][4]))
+        print("wrote", args.out, "(%d poses, %d of them with a negative score, best score %f)" %
+              (len(docker.top_list), sum(e[4] < 0 for e in docker.top_list), docker.top_list[0][4]))
     native = None
     if args.native is not None:
         from deeplocalproteindocking_amd.Results.InterfaceSelection import native_reference
