@@ -59,6 +59,9 @@ SIGNATURES = {
     "dlpd_receptor_packed_floats": (_ll, [_i, _i]),
     "dlpd_receptor_pack": (_i, [_p, _p, _i, _i, _p]),
     "dlpd_xy_correlate_packed": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "dlpd_receptor_ordered_floats": (_ll, [_i, _i]),
+    "dlpd_receptor_order": (_i, [_p, _p, _i, _i, _p]),
+    "dlpd_xy_correlate_ordered": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "dlpd_quads_floats": (ctypes.c_size_t, [_i, _i]),
     "dlpd_make_quads": (_i, [_p, _p, _i, _i, _p]),
     "dlpd_zfft_quads": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),

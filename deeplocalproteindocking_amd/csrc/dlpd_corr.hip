@@ -1116,6 +1116,9 @@ long long dlpd_k2_packed_receptor_floats(int CT, int L);
 int dlpd_k2_pack_receptor(const cplx* rec, void* packed, int CT, int L, hipStream_t st);
 int dlpd_k2_correlate_packed(const cplx* A, const cplx* packed, cplx* out, int CT, int nb, int L, hipStream_t st,
                              const unsigned char* pmap = nullptr, int nmasked = 0);
+long long dlpd_k2_ordered_receptor_floats(int CT, int L);
+int dlpd_k2_order_receptor(const cplx* rec, cplx* ordered, int CT, int L, hipStream_t st);
+int dlpd_k2_correlate_ordered(const cplx* A, const cplx* ordered, cplx* out, int CT, int nb, int L, hipStream_t st);
 
 template <int N, int HP, int MODE> static int launch_k3(const cplx* Bw, float* out, int CT, int C, int has_clash,
                                                         int nb, const float* W1t, const float* b1, const float* W2,
@@ -1384,6 +1387,16 @@ int dlpd_receptor_pack(const void* rec, void* packed, int CT, int L, void* strea
 int dlpd_xy_correlate_packed(const void* wsA, const void* rec_packed, void* wsB, int nb, int CT, int L, void* stream) {
   if (!wsA || !rec_packed || !wsB || nb <= 0 || CT <= 0) return DLPD_ERR_ARG;
   return dlpd_k2_correlate_packed((const cplx*)wsA, (const cplx*)rec_packed, (cplx*)wsB, CT, nb, L, (hipStream_t)stream);
+}
+// The same for boxes 64 and 32, whose K2 is the slab kernel: the copy in the order its column phase fetches the receptor
+long long dlpd_receptor_ordered_floats(int CT, int L) { return dlpd_k2_ordered_receptor_floats(CT, L); }
+int dlpd_receptor_order(const void* rec, void* ordered, int CT, int L, void* stream) {
+  if (!rec || !ordered || CT <= 0) return DLPD_ERR_ARG;
+  return dlpd_k2_order_receptor((const cplx*)rec, (cplx*)ordered, CT, L, (hipStream_t)stream);
+}
+int dlpd_xy_correlate_ordered(const void* wsA, const void* rec_ordered, void* wsB, int nb, int CT, int L, void* stream) {
+  if (!wsA || !rec_ordered || !wsB || nb <= 0 || CT <= 0) return DLPD_ERR_ARG;
+  return dlpd_k2_correlate_ordered((const cplx*)wsA, (const cplx*)rec_ordered, (cplx*)wsB, CT, nb, L, (hipStream_t)stream);
 }
 // ... going by a per-rotation pencil map (dlpd_rotated_occupancy's second output) for channels [0, nmasked): pencils the map
 // marks empty are not read from wsA (K1 with skip_empty did not write them); the packed-receptor boxes only

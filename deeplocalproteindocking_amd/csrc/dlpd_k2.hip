@@ -46,6 +46,14 @@
 // rotation are written out (not a loop of two): the first has no receptor request and rv is dead from its multiply on.
 // -DDLPD_K2_SET_PINGPONG=0: the loop over the two sets as it was, behind the per-set lambda (fixed order, two fetches; the
 // bit-equality reference of tests/test_k2_set_order_gpu.py and the A/B baseline).  EXPERIMENTS.md, section K2-SETORDER.
+// RECEPTOR IN CONSUMPTION ORDER (PK = 1, shared receptor, untransposed launches; N = 128 / 64).  k_pack_rec_order copies the
+// spectrum once per receptor to [slab][column set][instruction][lane]; fetch_rec then reads 512 contiguous bytes per
+// instruction from one base plus immediates instead of eight 64-byte runs at sixteen computed addresses.  Same values, same
+// registers.  A receptor per rotation and transposed launches keep the natural layout (PK = 0).
+// The A ROWS STAY STAGED: loading the inputs of the pruned first y pass straight into the butterfly's registers (lane (q, t):
+// elements t + 8r of row 8w + q, eight 8-byte loads in 64-byte pieces instead of four 16-byte ones, no staging stores and no
+// first-pass LDS reads) was built and measured 0.25 - 0.35 ms SLOWER per launch of 32 rotations at N = 128, and taken out.
+// EXPERIMENTS.md, section K2-OPERANDS.
 // ------------------------------------------------------------------------------------------
 #ifndef DLPD_K2_SET_PINGPONG
 #define DLPD_K2_SET_PINGPONG 1
@@ -79,7 +87,7 @@ template <int RS, int GS, int GX> struct ColAddrG {
   int base;      // swz(col)
   DLPD_HD int operator()(int e) const { return e * RS + ((e >> GS) & 1) * GX + base; }
 };
-template <int N, int MODE> __global__ void __launch_bounds__(DLPD_K2_THREADS(N))
+template <int N, int MODE, int PK = 0> __global__ void __launch_bounds__(DLPD_K2_THREADS(N))
 k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __restrict__ out,
           int CT, int nb, int nsplit, long long rec_bstride, float scale, int transposed) {
   constexpr int L = N / 2, NZ = N / 2 + 1, RS = N + 8;
@@ -101,6 +109,7 @@ k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __rest
   // register hand-over forward-x pass 2 -> inverse-x pass 1 (power-of-two plans only)
   constexpr bool HANDOVER = InvP1::PER == 1 && InvP1::NBF == T && (R1 % T == 0) && FwdP2::NBF <= R1;
   // row-group shift (above): power-of-two plans only (N = 80 keeps its blocked intermediates instead)
+  static_assert(PK == 0 || (MODE == 1 && N != 80), "the receptor in consumption order: correlate mode, power-of-two plans");
   constexpr int GX = (DLPD_K2_ROWSHIFT && N != 80) ? 8 : 0, GS = (R1 == 16) ? 4 : 3;
   static_assert(GX == 0 || ((1 << GS) == R1 && R1 >= 8 && RS >= N + GX), "groups of R1 rows, a wave's 8 rows in one group");
   DLPD_DYN_SHARED(cplx, S);
@@ -200,6 +209,17 @@ k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __rest
 
   cplx rv[FwdP2::PER][R2];
   auto fetch_rec = [&](int bb, int set) {
+    if constexpr (PK) {
+      // [slab][set][instruction i * R2 + q][lane]: one base, the rest immediates
+      int off = set * (8 * N) + lane;
+      DLPD_OPAQUE(off);
+      const cplx* p = rec + ((size_t)c * NZ + kz) * N * N + (unsigned)off;
+#pragma unroll
+      for (int i = 0; i < FwdP2::PER; i++)
+#pragma unroll
+        for (int q = 0; q < R2; q++) rv[i][q] = p[(i * R2 + q) * 64];
+      return;
+    }
     const cplx* rbase = rec + (size_t)bb * rec_bstride + ((size_t)c * NZ + kz) * N * N;
     int col = set * 8 + c8;
     DLPD_OPAQUE(col);                  // keeps the 16 load addresses from being hoisted out of the batch loop (spills)
@@ -378,18 +398,34 @@ k_xy_corr(const cplx* __restrict__ A, const cplx* __restrict__ rec, cplx* __rest
 #endif
 static constexpr int k2_nsplit_override() { return DLPD_K2_NSPLIT; }
 
-template <int N, int MODE> static int launch_k2(const cplx* A, const cplx* rec, cplx* out, int CT, int nb,
-                                                long long rbs, float scale, hipStream_t st, int transposed = 0) {
+template <int N, int MODE, int PK = 0> static int launch_k2(const cplx* A, const cplx* rec, cplx* out, int CT, int nb,
+                                                            long long rbs, float scale, hipStream_t st, int transposed = 0) {
   constexpr int NZ = N / 2 + 1, RS = N + 8;
   const size_t shmem = (size_t)((N + (N == 80 ? 8 : 0)) * RS + N) * sizeof(cplx);
-  int rc = dlpd_set_max_dyn_shared((const void*)k_xy_corr<N, MODE>, shmem);
+  int rc = dlpd_set_max_dyn_shared((const void*)k_xy_corr<N, MODE, PK>, shmem);
   if (rc) return rc;
   int nsplit = (MODE == 1 && nb >= 8) ? 2 : 1;
   if (k2_nsplit_override()) nsplit = k2_nsplit_override();
   const int slabs8 = ((NZ * CT + 7) / 8) * 8;
   dim3 grid(slabs8 * nsplit), block(DLPD_K2_THREADS(N));
-  DLPD_LAUNCH((k_xy_corr<N, MODE>), grid, block, shmem, st, A, rec, out, CT, nb, nsplit, rbs, scale, transposed);
+  DLPD_LAUNCH((k_xy_corr<N, MODE, PK>), grid, block, shmem, st, A, rec, out, CT, nb, nsplit, rbs, scale, transposed);
   return dlpd_check_launch();
+}
+
+// The receptor spectrum (CT, NZ, N, N) in the order fetch_rec<PK = 1> reads it: ord[slab][set][i * R2 + q][lane] =
+// rec[slab][kx = FwdP2::out_index(i, q, lane >> 3)][ky = 8 * set + (lane & 7)].  A permutation within each slab.
+template <int N> __global__ void __launch_bounds__(256)
+k_pack_rec_order(const cplx* __restrict__ rec, cplx* __restrict__ ord, long long total) {
+  constexpr int R1 = FftPlanW<N>::R1, R2 = FftPlanW<N>::R2;
+  typedef FftPassW<N, R2, R1, -1, 8> FwdP2;
+  static_assert(FwdP2::FULL && FwdP2::PER * R2 * 64 == 8 * N, "a set's values: PER * R2 instructions of 64 lanes");
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const long long slab = e / (N * N);
+  const int w = (int)(e % (N * N)), set = w / (8 * N), k = (w / 64) % (FwdP2::PER * R2), lane = w & 63;
+  FwdP2 idx;
+  const int kx = idx.out_index(k / R2, k % R2, lane >> 3), ky = 8 * set + (lane & 7);
+  ord[e] = rec[slab * (N * N) + kx * N + ky];
 }
 
 
@@ -802,6 +838,33 @@ int dlpd_k2_correlate_packed(const cplx* A, const cplx* packed, cplx* out, int C
                              const unsigned char* pmap, int nmasked) {
   if (!dlpd_k2_packed_receptor_floats(CT, L)) return DLPD_ERR_UNSUPPORTED;
   return dlpd_k2q_correlate(A, packed, out, CT, nb, L, 0, k2_nsplit_override(), st, 1, pmap, nmasked);
+}
+
+// ... and for the boxes whose K2 is k_xy_corr itself (64 / 32): the copy in fetch_rec's order (k_pack_rec_order)
+// (-DDLPD_K2_REC_ORDERED=0: no such copy anywhere, the size query answers 0 and the engine reads the natural layout)
+#ifndef DLPD_K2_REC_ORDERED
+#define DLPD_K2_REC_ORDERED 1
+#endif
+#define DLPD_K2_ORDERED_BOXES 32, 64
+long long dlpd_k2_ordered_receptor_floats(int CT, int L) {
+  if (!DLPD_K2_REC_ORDERED || !dlpd_listed<DLPD_K2_ORDERED_BOXES>(L) || CT <= 0) return 0;
+  return (long long)CT * (L + 1) * (2 * L) * (2 * L) * 2;
+}
+int dlpd_k2_order_receptor(const cplx* rec, cplx* ordered, int CT, int L, hipStream_t st) {
+  if (!dlpd_k2_ordered_receptor_floats(CT, L)) return DLPD_ERR_UNSUPPORTED;
+  return dlpd_dispatch<DLPD_K2_ORDERED_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    const long long total = (long long)CT * (N / 2 + 1) * N * N;
+    DLPD_LAUNCH((k_pack_rec_order<N>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, rec, ordered, total);
+    return dlpd_check_launch();
+  });
+}
+int dlpd_k2_correlate_ordered(const cplx* A, const cplx* ordered, cplx* out, int CT, int nb, int L, hipStream_t st) {
+  if (!dlpd_k2_ordered_receptor_floats(CT, L)) return DLPD_ERR_UNSUPPORTED;
+  return dlpd_dispatch<DLPD_K2_ORDERED_BOXES>(L, [&](auto l) {
+    constexpr int N = 2 * l();
+    return launch_k2<N, 1, 1>(A, ordered, out, CT, nb, 0, 1.f, st, 0);
+  });
 }
 
 int dlpd_k2_orientation_supported(int L) { return dlpd_listed<DLPD_K2_ORIENTED_BOXES>(L) ? 1 : 0; }

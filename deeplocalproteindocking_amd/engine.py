@@ -199,6 +199,10 @@ class _Grid:
         self.recP = torch.zeros(npk, dtype=f32, device=dev) if npk else None
         self.recF = None if (eng._spectrum_is_temporary and self.recP is not None) else \
             torch.zeros(CT, NZ, N, N, 2, dtype=f32, device=dev)
+        # boxes 64 / 32 (K2 keeps a rotation's receptor values in registers): a copy in the order of K2's receptor fetches
+        # (include/dlpd.h: dlpd_receptor_order), read by untransposed launches; the natural spectrum stays for the others
+        nord = lib.call("dlpd_receptor_ordered_floats", CT, L) if packed_receptor else 0
+        self.recO = torch.zeros(nord, dtype=f32, device=dev) if nord else None
         self.wsA = torch.empty(nb * CT * NZ * L * L * 2, dtype=f32, device=dev)
         self.wsB = torch.empty(nb * CT * NZ * N * N * 2, dtype=f32, device=dev)
         # sparse K1: the ligand's cell map, the per-rotation maps, their pencil words (K2 goes by them where it reads
@@ -378,6 +382,7 @@ class DockingEngine:
                 "exclusion": int(self.exclusion),
                 "restraints": None if self.restraints is None else (self.restraints.J, self.restraints.need),
                 "k2_packed_receptor": {"fine": fine.recP is not None, "coarse": bool(c and c.recP is not None)},
+                "k2_ordered_receptor": {"fine": fine.recO is not None, "coarse": bool(c and c.recO is not None)},
                 "embedded_extent": self.extent or None,
                 "k1_occupancy_maps": {"fine": fine.sparse, "coarse": bool(c and c.sparse),
                                       "k2_pencil_map": {"fine": fine.pencil_map, "coarse": bool(c and c.pencil_map)},
@@ -431,6 +436,8 @@ class DockingEngine:
             self.lib.call("dlpd_rfft3d_padded", _ptr(r), _ptr(recF), _ptr(g.wsA), g.CT, g.L, 1.0 / float(g.N) ** 3, st)
             if g.recP is not None:
                 self.lib.call("dlpd_receptor_pack", _ptr(recF), _ptr(g.recP), g.CT, g.L, st)
+            if g.recO is not None:
+                self.lib.call("dlpd_receptor_order", _ptr(recF), _ptr(g.recO), g.CT, g.L, st)
 
     SPARSE_K1_MAX_FILL = 0.7
 
@@ -541,6 +548,8 @@ class DockingEngine:
             self.lib.call("dlpd_xy_correlate_packed_occ", _ptr(g.wsA), _ptr(g.recP), _ptr(g.wsB), nb, g.CT, g.L, _ptr(pen), g.C, st)
         elif g.recP is not None and not tr:
             self.lib.call("dlpd_xy_correlate_packed", _ptr(g.wsA), _ptr(g.recP), _ptr(g.wsB), nb, g.CT, g.L, st)
+        elif g.recO is not None and not tr:
+            self.lib.call("dlpd_xy_correlate_ordered", _ptr(g.wsA), _ptr(g.recO), _ptr(g.wsB), nb, g.CT, g.L, st)
         else:
             if g.recF is None:       # (packed-receptor boxes drop the natural-layout spectrum: keep_receptor_spectrum=True keeps it)
                 raise RuntimeError("dlpd: this engine holds only the packed receptor spectrum; a transposed launch needs "

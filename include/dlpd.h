@@ -14,6 +14,7 @@
  * THE PATH -- the minimal call set of one search (Docker.py:184-238; what DockingEngine issues in steady state):
  *   once per pair    dlpd_rfft3d_padded        receptor spectrum            (DockingModels.py:71, hoisted out of the loop)
  *                    dlpd_receptor_pack        ... in K2's read order       (boxes 80 / 40 only)
+ *                    dlpd_receptor_order       ... in K2's fetch order      (boxes 64 / 32 only)
  *                    dlpd_make_channels_last   ligand copy K1 gathers from
  *   per launch       dlpd_zfft_channels_last   K1: rotation + z transform  (Docker.py:218)
  *                    dlpd_project_atoms + dlpd_zfft_into   clash channel from rotated atoms (Docker.py:221-224)
@@ -253,6 +254,16 @@ int dlpd_xy_correlate(const void* wsA, const void* rec, void* wsB, int nb, int C
 long long dlpd_receptor_packed_floats(int CT, int L);
 int dlpd_receptor_pack(const void* rec, void* packed, int CT, int L, void* stream);
 int dlpd_xy_correlate_packed(const void* wsA, const void* rec_packed, void* wsB, int nb, int CT, int L, void* stream);
+
+/* The same for boxes 64 and 32, whose K2 keeps a rotation's receptor values in registers and fetches one column set's
+ * worth per rotation: dlpd_receptor_order copies the spectrum ONCE into the order of those fetches ([slab][column set]
+ * [instruction][lane]: 512 contiguous bytes per instruction from one base address instead of eight 64-byte runs at
+ * computed addresses), dlpd_xy_correlate_ordered reads that copy (untransposed slabs, one receptor for the batch).  Same
+ * arithmetic, same results bit for bit.  dlpd_receptor_ordered_floats: floats of the copy (as many as the spectrum), 0
+ * for every other box. */
+long long dlpd_receptor_ordered_floats(int CT, int L);
+int dlpd_receptor_order(const void* rec, void* ordered, int CT, int L, void* stream);
+int dlpd_xy_correlate_ordered(const void* wsA, const void* rec_ordered, void* wsB, int nb, int CT, int L, void* stream);
 
 /* VolumeConvolution (Docker.py:32,225; DockingModels.py:48,71) for ANY box size -- `box_size` is a free constructor
  * argument of the reference's Docker (Docker.py:18,22-24,31): out (nvol, N^3)[t mod N] = sum_r v1[r + t] v2[r], N = 2L,
