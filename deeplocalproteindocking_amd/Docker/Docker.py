@@ -748,6 +748,143 @@ class Docker:
                                          zip(ev["irmsd"], ev["lrmsd"], ev["fnat"], ev["capri"])) + "\n")
         self.log.flush()
 
+    # ------------------------------------------------------------------ interface consensus (csrc/dlpd_interface.h; build-defined)
+    @staticmethod
+    def _complex_residues(complex):
+        rr, lr = getattr(complex, "rec_residues", None), getattr(complex, "lig_residues", None)
+        if getattr(complex, "all", None) is None or rr is None or lr is None:
+            raise RuntimeError("dlpd: the interface steps need a ComplexReference (Results.InterfaceSelection.complex_reference) or a "
+                               "native reference built with all_contacts=True")
+        return list(rr), list(lr)
+
+    def _interface_weights(self, poses, weights, temperature):
+        """-> float64 weights of the poses on the host (the doc of ``interface``)"""
+        K = len(poses)
+        if isinstance(weights, str):
+            if weights == "uniform":
+                return np.full(K, 1.0 / K, dtype=np.float64)
+            if weights == "rank":
+                w = 1.0 / (1.0 + np.arange(K, dtype=np.float64))
+                return w / w.sum()
+            if weights == "boltzmann":
+                if temperature is None or not float(temperature) > 0.0:
+                    raise Exception("boltzmann weights need a temperature > 0", temperature)
+                s = np.array([float(e[4]) if np.ndim(e[0]) == 0 else float(e[2]) for e in poses], dtype=np.float64)
+                w = np.exp(-(s - s.min()) / float(temperature))
+                return w / w.sum()
+            raise Exception("Unknown interface weights", weights)
+        w = np.asarray(weights.detach().cpu().numpy() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
+        if len(w) != K:
+            raise Exception("interface weights must be one number per pose", len(w), K)
+        return w
+
+    def _interface_bits_of(self, complex, poses):
+        """the residue bitmaps of ``poses``; those of the last ``interface`` call are reused for the same list object"""
+        from deeplocalproteindocking_amd import ops
+        held = getattr(self, "_interface_of", None)
+        if held is not None and held[0] is poses and held[1] is complex and len(poses) == held[2]:
+            return self.interface_bits
+        if len(poses) > ops.POSE_CLUSTER_MAX:
+            raise RuntimeError("dlpd: the interface steps take at most %d poses, got %d" % (ops.POSE_CLUSTER_MAX, len(poses)))
+        complex.to(self.device)
+        P = self.dat_frame_poses(poses)
+        self.interface_bits = ops.pose_interface_bits(P, complex, float(complex.contact_dist), lib=self._lib)
+        self._interface_of = (poses, complex, len(poses))
+        return self.interface_bits
+
+    def interface(self, complex, poses=None, weights="uniform", temperature=None):
+        """Which residues of each protein a list of poses puts in the interface (default: ``self.top_list``; ``refined_list``
+        and ``clustered_list`` entries are taken too; none of the lists is touched).  ``complex``: a ``ComplexReference`` of the
+        two unbound files (Results.InterfaceSelection.complex_reference), or a native reference built with
+        ``all_contacts=True``.  A residue is in a pose's interface iff one of its atoms lies within ``complex.contact_dist`` of
+        an atom of the partner.  ``weights``: "uniform" (1 / K each); "boltzmann": exp(-(s - s_min) / ``temperature``)
+        normalised to sum 1 (``temperature`` required, in the units of the score); "rank": 1 / (1 + position) normalised;
+        or K numbers taken as they are -- float64 on the host in every case.
+        -> ``self.interface_profile``, a dict of numpy arrays ``rec_freq`` / ``lig_freq`` (float64: the summed weights of the
+        poses that mark a residue), ``rec_count`` / ``lig_count`` (int32: their number), with ``rec_residues`` /
+        ``lig_residues`` ((chain, resnum, name), in the arrays' order) and ``K``; and ``self.interface_bits``, the two bitmaps
+        on the device (ops.pose_interface_bits; ops.unpack_bits for host filters).  An empty list gives empty bitmaps and zeros
+        without a launch.  At most 65,536 poses.  Every rank treats the same (gathered) list; there is no collective here."""
+        from deeplocalproteindocking_amd import ops
+        poses = self.top_list if poses is None else poses
+        rr, lr = self._complex_residues(complex)
+        self._interface_of = None
+        bits = self._interface_bits_of(complex, poses)
+        w = self._interface_weights(poses, weights, temperature) if len(poses) else None
+        got = ops.interface_profile(bits[0], bits[1], len(rr), len(lr), w, lib=self._lib)
+        self.interface_profile = {k: v.cpu().numpy() for k, v in zip(("rec_freq", "lig_freq", "rec_count", "lig_count"), got)}
+        self.interface_profile.update({"rec_residues": rr, "lig_residues": lr, "K": len(poses)})
+        return self.interface_profile
+
+    def interface_residues(self, side, n=None, min_freq=None):
+        """The residues of one side ("receptor" / "ligand", or "R" / "L") of ``self.interface_profile`` that some pose marks,
+        sorted by falling frequency, ties in file order; ``n``: at most that many; ``min_freq``: only those at or above it.
+        -> "CHAIN:RESNUM" strings ("_" for a blank chain), the selections ``restraints_from_selections`` takes."""
+        prof = getattr(self, "interface_profile", None)
+        if not isinstance(prof, dict):
+            raise RuntimeError("dlpd: interface_residues needs Docker.interface first")
+        key = {"receptor": "rec", "r": "rec", "rec": "rec", "ligand": "lig", "l": "lig", "lig": "lig"}.get(str(side).lower())
+        if key is None:
+            raise Exception("Unknown side", side)
+        freq, count, residues = prof[key + "_freq"], prof[key + "_count"], prof[key + "_residues"]
+        order = [int(i) for i in np.argsort(-freq, kind="stable") if count[i] > 0 and (min_freq is None or freq[i] >= float(min_freq))]
+        if n is not None:
+            order = order[:int(n)]
+        return ["%s:%d" % (residues[i][0] if str(residues[i][0]).strip() else "_", residues[i][1]) for i in order]
+
+    def cluster_interface(self, complex, poses=None, threshold=None, keep=None, rank="score"):
+        """``cluster`` with the similarity of two poses' interfaces in place of the RMSD between them: poses i and j are
+        neighbours iff the residue sets they put in the interface (both proteins' together) have a Jaccard index
+        |A & B| / |A | B| >= ``threshold`` (in [0, 1], required: there is no default; compared as the integer
+        round(1024 threshold)); two poses without an interface are neighbours.  Same greedy scan in list order, same ``keep``
+        and ``rank``, same ``self.clustered_list`` / ``self.cluster_labels``: the writer, ``evaluate`` and ``refine`` take the
+        result unchanged.  The bitmaps of ``self.interface_bits`` are reused when ``interface`` was run on the same list
+        object and complex."""
+        from deeplocalproteindocking_amd import ops
+        if threshold is None or not 0.0 <= float(threshold) <= 1.0:
+            raise Exception("cluster_interface needs a threshold in [0, 1] (a Jaccard index); there is no default", threshold)
+        if rank not in ("score", "size"):
+            raise Exception("Unknown cluster ranking", rank)
+        if keep is not None and int(keep) <= 0:
+            raise Exception("cluster keep must be positive", keep)
+        poses = self.top_list if poses is None else poses
+        self._complex_residues(complex)
+        self.clustered_list, self.cluster_labels = [], np.zeros(0, dtype=np.int32)
+        if not len(poses):
+            return self.clustered_list
+        bits = self._interface_bits_of(complex, poses)
+        R, _, own, score = self._pose_arrays([e[:4] if (len(e) == 5 and np.ndim(e[0]) != 0) else e for e in poses])
+        first = None if rank == "size" or keep is None else int(keep)
+        centres, sizes, labels = ops.interface_cluster(bits[0], bits[1], float(threshold), max_clusters=first, lib=self._lib)
+        centres, sizes, labels = centres.cpu().numpy(), sizes.cpu().numpy(), labels.cpu().numpy()
+        order = np.arange(len(centres))
+        if rank == "size":
+            order = np.argsort(-sizes.astype(np.int64), kind="stable")
+            if keep is not None:
+                order = order[:int(keep)]
+            place = np.full(len(centres) + 1, -1, dtype=np.int32)          # (the last slot: label -1 stays -1)
+            place[order] = np.arange(len(order), dtype=np.int32)
+            labels = place[labels]
+        self.clustered_list = [(R[c].copy(), own[c], score[c], int(c), int(sizes[n])) for n, c in ((n, int(centres[n])) for n in order)]
+        self.cluster_labels = labels.astype(np.int32)
+        return self.clustered_list
+
+    def write_interface(self):
+        """``self.interface_profile`` into the open log, one line per residue that some pose marks: R or L, chain, residue number,
+        name, count, frequency (``%f``), tab-separated; the receptor's residues first, each side in file order"""
+        if self.log is None:
+            return
+        prof = getattr(self, "interface_profile", None)
+        rows = []
+        if isinstance(prof, dict):
+            for tag, key in (("R", "rec"), ("L", "lig")):
+                for res, c, f in zip(prof[key + "_residues"], prof[key + "_count"], prof[key + "_freq"]):
+                    if c > 0:
+                        rows.append("%s\t%s\t%d\t%s\t%d\t%f" % (tag, res[0], res[1], res[2], c, f))
+        if rows:
+            self.log.write("\n".join(rows) + "\n")
+        self.log.flush()
+
     def refine_prepared(self, prepared, perturbations=None, radius=1, poses=None):
         """``refine`` for a target given as files: the ``PreparedPair`` the SE3 search ran on (``prepare`` / ``dockSE3``) holds
         the volumes; the clash channel is re-projected from the rotated ligand atoms as ``dockSE3`` does (Docker.py:221-224)."""

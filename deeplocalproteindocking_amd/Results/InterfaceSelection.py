@@ -335,6 +335,8 @@ def native_reference_from_points(pairs, ligand_ca, target_ca, rec_atoms, lig_ato
     if (all_rec is None) != (all_lig is None) or (all_rec is None) != (all_pairs is None):
         raise RuntimeError("dlpd: all_rec, all_lig and all_pairs go together")
     tables = None if all_rec is None else ops.contact_tables(all_rec[0], all_rec[1], all_lig[0], all_lig[1], all_pairs)
+    host.setdefault("rec_residues", None)                                               # (named by native_reference(all_contacts=True))
+    host.setdefault("lig_residues", None)
     return NativeReference(moments_host=moments, counts=counts, rec_atoms64=np.asarray(rec_atoms, dtype=np.float64).reshape(-1, 3),
                            lig_atoms64=np.asarray(lig_atoms, dtype=np.float64).reshape(-1, 3), ranges_host=ranges, C=int(ranges.shape[0]),
                            contact_dist=float(contact_dist), pairs=pairs, ligand_ca=ligand_ca, target_ca=target_ca, all=tables, **host)
@@ -397,9 +399,38 @@ def native_reference(bound_receptor, bound_ligand, unbound_receptor, unbound_lig
     if all_contacts:
         ra, ro, rindex = _packed_standard_atoms(ur, shift_r)
         la, lo, lindex = _packed_standard_atoms(ul, shift_l)
-        extra = dict(all_rec=(ra, ro), all_lig=(la, lo), all_pairs=[(rindex[r[:2]], lindex[l[:2]]) for r, l in contacts])
+        extra = dict(all_rec=(ra, ro), all_lig=(la, lo), all_pairs=[(rindex[r[:2]], lindex[l[:2]]) for r, l in contacts],
+                     rec_residues=_all_residues(ur), lig_residues=_all_residues(ul))
     return native_reference_from_points(pairs, ligand_ca, target_ca, rec_atoms, lig_atoms, ranges, contact_dist, interfaces=interfaces,
                                         superposition=(Q, s), contacts=contacts, bound_contacts=bound_pairs, **extra)
+
+
+class ComplexReference(object):
+    """What the interface kernels (csrc/dlpd_interface.h) need of one target when there is no native: ``all``, the
+    tables of ops.contact_tables over every ATOM record of every standard residue of the two unbound structures (no native
+    pairs), in the frames of ``native_reference``; ``rec_residues`` / ``lig_residues``, the residues as (chain, resnum, name)
+    in the order of the bitmaps' bits; ``contact_dist``.  ``to(device)`` moves the tables.  A ``NativeReference`` built with
+    ``all_contacts=True`` carries the same three and is taken wherever this is."""
+
+    def __init__(self, tables, rec_residues, lig_residues, contact_dist):
+        self.all, self.rec_residues, self.lig_residues, self.contact_dist = tables, list(rec_residues), list(lig_residues), float(contact_dist)
+        self.device = torch.device("cpu")
+
+    def to(self, device):
+        for name in ALL_CONTACT_TENSORS:
+            self.all[name] = self.all[name].to(device)
+        self.device = self.all["rec_atoms"].device
+        return self
+
+
+def complex_reference(unbound_receptor, unbound_ligand, contact_dist=5.0):
+    """The ``ComplexReference`` of two unbound structures (as ``read_structure`` gives them, or file names): each about its own
+    bounding-box centre, the ligand then placed by the pose -- the frame of a .dat file."""
+    from deeplocalproteindocking_amd import ops
+    ur, ul = (read_structure(s) if isinstance(s, str) else s for s in (unbound_receptor, unbound_ligand))
+    ra, ro, _ = _packed_standard_atoms(ur, -bbox_centre(ur))
+    la, lo, _ = _packed_standard_atoms(ul, -bbox_centre(ul))
+    return ComplexReference(ops.contact_tables(ra, ro, la, lo, ()), _all_residues(ur), _all_residues(ul), contact_dist)
 
 
 def conformation_poses(conformations):

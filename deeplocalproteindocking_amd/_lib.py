@@ -135,6 +135,11 @@ SIGNATURES = {
     "dlpd_pose_native_contacts": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _f, _p, _p]),
     "dlpd_pose_capri": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
     "dlpd_pose_contacts_all": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _p]),
+    "dlpd_pose_residue_bits": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _f, _f, _p, _p, _p]),
+    "dlpd_interface_profile_ws": (_sz, [_i, _i, _i]),
+    "dlpd_interface_profile": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "dlpd_interface_within": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
+    "dlpd_interface_cluster": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 ERRORS = {1: "DLPD_ERR_ARG (bad pointer/size)", 2: "DLPD_ERR_UNSUPPORTED (size not compiled)",

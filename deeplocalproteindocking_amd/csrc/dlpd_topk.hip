@@ -577,6 +577,9 @@ int dlpd_topk_merge_tau(const float* cand_score, const int* cand_idx, const int*
 // every residue contact of the posed complex, for fnonnat: shares the predicate of dlpd_evaluate.h
 #include "dlpd_contacts.h"
 
+// the interface of every pose as residue bitmaps (build-defined): residue frequencies over a list, clustering by interface
+#include "dlpd_interface.h"
+
 // exclusion radius of the search (build-defined): local-minimum suppression of V and of K3's candidate lists
 #include "dlpd_suppress.h"
 

@@ -1399,3 +1399,163 @@ def fnonnat_of(n_dec, n_corr):
 def pose_fnonnat(poses, native, lib=None):
     """fnonnat (K) float64 on the poses' device: the share of a pose's residue contacts that the native complex does not have"""
     return fnonnat_of(*pose_contact_counts(poses, native, lib=lib))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The interface of every pose as residue bitmaps: frequencies over a list, clustering by interface (csrc/dlpd_interface.h;
+# DESIGN.md 4n; build-defined)
+# ----------------------------------------------------------------------------------------------------------------------
+INTERFACE_Q_ONE = 1024
+
+
+def _contact_tables_on(tables, dev, lib):
+    """the tensors of ``contact_tables`` (a dict, or an object that carries one as ``.all``) checked against each other"""
+    tb = tables if isinstance(tables, dict) else getattr(tables, "all", None)
+    if tb is None:
+        raise RuntimeError("dlpd: pose_interface_bits needs the tables of ops.contact_tables (a ComplexReference, or a native "
+                           "reference built with all_contacts=True)")
+    ra, la = _on(tb["rec_atoms"], torch.float32, dev, "rec_atoms", lib), _on(tb["lig_atoms"], torch.float32, dev, "lig_atoms", lib)
+    ro, lo = _on(tb["rec_off"], torch.int32, dev, "rec_off", lib), _on(tb["lig_off"], torch.int32, dev, "lig_off", lib)
+    rs, ls = _on(tb["rec_sph"], torch.float32, dev, "rec_sph", lib), _on(tb["lig_sph"], torch.float32, dev, "lig_sph", lib)
+    roh, loh = tb["rec_off_host"], tb["lig_off_host"]
+    NRa, NLa, NRres, NLres = ra.shape[0], la.shape[0], roh.shape[0] - 1, loh.shape[0] - 1
+    if ro.numel() != NRres + 1 or lo.numel() != NLres + 1 or tuple(rs.shape) != (NRres, 4) or tuple(ls.shape) != (NLres + 1, 4) \
+            or int(roh[-1]) != NRa or int(loh[-1]) != NLa:
+        raise RuntimeError("dlpd: these contact tables do not belong together")
+    return tb, ra, ro, rs, la, lo, ls, roh, loh
+
+
+def pose_interface_bits(poses, tables, cutoff, lib=None):
+    """(rec_bits (K, ceil(NRres / 32)), lig_bits (K, ceil(NLres / 32))) int32 on the poses' device: bit (i & 31) of word i >> 5 of
+    row k is set iff residue i of that protein has an atom within ``cutoff`` of some atom of the partner under pose k -- every
+    atom of both, the predicate of ``pose_contact_counts`` bit for bit; the bits past the last residue are zero.  ``tables``:
+    the dict of ``contact_tables`` (its native pairs are not read) or an object that carries it as ``.all``, on the poses'
+    device (an array of poses is moved to the tables').  No poses: empty bitmaps, no launch."""
+    import numpy as np
+    tb = tables if isinstance(tables, dict) else getattr(tables, "all", None)
+    if not torch.is_tensor(poses):
+        poses = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 12)))
+        if tb is not None:
+            poses = poses.to(tb["rec_atoms"].device)
+    dev = poses.device
+    tb, ra, ro, rs, la, lo, ls, roh, loh = _contact_tables_on(tables, dev, lib)
+    NRres, NLres = roh.shape[0] - 1, loh.shape[0] - 1
+    K = poses.shape[0]
+    if K > POSE_CLUSTER_MAX:
+        raise RuntimeError("dlpd: pose_interface_bits takes at most %d poses, got %d" % (POSE_CLUSTER_MAX, K))
+    rec_bits = torch.empty(K, (NRres + 31) // 32, dtype=torch.int32, device=dev)
+    lig_bits = torch.empty(K, (NLres + 31) // 32, dtype=torch.int32, device=dev)
+    if K == 0:
+        return rec_bits, lig_bits
+    lib_ = lib or get_lib()
+    poses = _poses64(poses, lib)
+    lib_.call("dlpd_pose_residue_bits", _ptr(poses), K, _ptr(ra), _ptr(ro), _ptr(rs), ra.shape[0], NRres, _ptr(la), _ptr(lo), _ptr(ls),
+              la.shape[0], NLres, roh.ctypes.data, loh.ctypes.data, float(tb["lig_extent"]), float(cutoff), _ptr(rec_bits), _ptr(lig_bits),
+              _stream(dev))
+    return rec_bits, lig_bits
+
+
+def _interface_bits(rec_bits, lig_bits, lib):
+    if not (torch.is_tensor(rec_bits) and torch.is_tensor(lig_bits) and rec_bits.dtype == torch.int32 and lig_bits.dtype == torch.int32
+            and rec_bits.dim() == 2 and lig_bits.dim() == 2 and rec_bits.shape[0] == lig_bits.shape[0]
+            and rec_bits.device == lig_bits.device and (rec_bits.is_cuda or lib is not None)):
+        raise RuntimeError("dlpd: rec_bits (K, Wr) and lig_bits (K, Wl) must be int32 bitmaps of the same poses on one device "
+                           "(ops.pose_interface_bits); there is no CPU path")
+    return rec_bits.contiguous(), lig_bits.contiguous()
+
+
+def unpack_bits(bits, n):
+    """(K, W) int32 bitmap words -> (K, n) bool on the same device: column i is bit (i & 31) of word i >> 5"""
+    K = bits.shape[0]
+    if n > 32 * bits.shape[1]:
+        raise RuntimeError("dlpd: unpack_bits: %d words hold no %d bits" % (bits.shape[1], n))
+    shifts = torch.arange(32, dtype=torch.int32, device=bits.device)
+    return ((bits[:, :, None] >> shifts[None, None, :]) & 1).bool().reshape(K, -1)[:, :n]
+
+
+def interface_profile(rec_bits, lig_bits, NRres, NLres, weights=None, lib=None):
+    """Over the K poses of the two bitmaps -> (rec_freq (NRres), lig_freq (NLres) float64, rec_count, lig_count int32) on
+    their device: how many poses mark a residue, and the sum of ``weights`` (K numbers, any values; None: 1 / K each) over
+    those poses.  The sum's order depends on K alone -- chunks of 1,024 poses, ascending inside a chunk, the chunk partials
+    added in ascending order -- so two runs give the same bytes and a host loop in that order reproduces them.  No poses:
+    zeros, no launch."""
+    import numpy as np
+    rec_bits, lig_bits = _interface_bits(rec_bits, lig_bits, lib)
+    NRres, NLres = int(NRres), int(NLres)
+    K, dev = rec_bits.shape[0], rec_bits.device
+    if NRres < 1 or NLres < 1 or rec_bits.shape[1] != (NRres + 31) // 32 or lig_bits.shape[1] != (NLres + 31) // 32:
+        raise RuntimeError("dlpd: interface_profile: the bitmaps' widths are not those of %d and %d residues" % (NRres, NLres))
+    rec_freq, lig_freq = torch.zeros(NRres, dtype=torch.float64, device=dev), torch.zeros(NLres, dtype=torch.float64, device=dev)
+    rec_count, lig_count = torch.zeros(NRres, dtype=torch.int32, device=dev), torch.zeros(NLres, dtype=torch.int32, device=dev)
+    if K == 0:
+        return rec_freq, lig_freq, rec_count, lig_count
+    if weights is None:
+        w = torch.full((K,), 1.0 / K, dtype=torch.float64, device=dev)
+    else:
+        if not torch.is_tensor(weights):
+            weights = torch.from_numpy(np.ascontiguousarray(np.asarray(weights, dtype=np.float64)))
+        w = weights.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(w.shape) != (K,):
+            raise RuntimeError("dlpd: interface_profile weights must be %d numbers, one per pose" % K)
+    lib_ = lib or get_lib()
+    nbytes = lib_.call("dlpd_interface_profile_ws", K, NRres, NLres)
+    if nbytes == 0:
+        raise RuntimeError("dlpd: interface_profile takes at most %d poses, %d and %d residues" %
+                           (POSE_CLUSTER_MAX, CONT_MAX_RECEPTOR_RESIDUES, CONT_MAX_LIGAND_RESIDUES))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    lib_.call("dlpd_interface_profile", _ptr(rec_bits), _ptr(lig_bits), K, NRres, NLres, _ptr(w), _ptr(rec_freq), _ptr(lig_freq),
+              _ptr(rec_count), _ptr(lig_count), _ptr(ws), nbytes, _stream(dev))
+    return rec_freq, lig_freq, rec_count, lig_count
+
+
+def interface_q(threshold):
+    """the integer the kernels compare with: poses i, j are neighbours iff |F_i & F_j| * 1024 >= q * |F_i | F_j|,
+    q = round(1024 * threshold), threshold (a Jaccard index) in [0, 1]"""
+    t = float(threshold)
+    if not 0.0 <= t <= 1.0:
+        raise RuntimeError("dlpd: the interface similarity threshold is a Jaccard index in [0, 1], got %r" % (threshold,))
+    return int(round(t * INTERFACE_Q_ONE))
+
+
+def interface_within(rec_bits, lig_bits, threshold, lib=None):
+    """The neighbour bitmap of interface similarity alone, in the layout of ``pose_within``: (K, ceil(K / 64)) int64 words, bit
+    (j & 63) of word [i, j >> 6] set iff the residue sets of poses i and j (both proteins' together) have a Jaccard index
+    >= ``threshold`` (``interface_q``); two empty sets are neighbours.  For analysis and the tests."""
+    rec_bits, lig_bits = _interface_bits(rec_bits, lig_bits, lib)
+    q = interface_q(threshold)
+    K, dev = rec_bits.shape[0], rec_bits.device
+    mask = torch.empty(K, (K + 63) // 64, dtype=torch.int64, device=dev)
+    if K == 0:
+        return mask
+    (lib or get_lib()).call("dlpd_interface_within", _ptr(rec_bits) if rec_bits.shape[1] else None, _ptr(lig_bits) if lig_bits.shape[1] else None,
+                            K, rec_bits.shape[1], lig_bits.shape[1], q, _ptr(mask), _stream(dev))
+    return mask
+
+
+def interface_cluster(rec_bits, lig_bits, threshold, max_clusters=None, lib=None):
+    """Greedy clustering of a list, in ITS order, by the similarity of the poses' interfaces (``interface_within``): pose i is
+    a centre iff no earlier centre is its neighbour, every other pose joins the first centre that is.  -> (centres, sizes,
+    labels) as ``pose_cluster`` returns them; the K x K bitmap stays in a workspace on the device."""
+    rec_bits, lig_bits = _interface_bits(rec_bits, lig_bits, lib)
+    q = interface_q(threshold)
+    K, dev = rec_bits.shape[0], rec_bits.device
+    if K > POSE_CLUSTER_MAX:
+        raise RuntimeError("dlpd: interface_cluster takes at most %d poses, got %d" % (POSE_CLUSTER_MAX, K))
+    m = K if max_clusters is None else int(max_clusters)
+    if max_clusters is not None and m <= 0:
+        raise RuntimeError("dlpd: interface_cluster max_clusters must be positive")
+    m = min(m, K)
+    centres = torch.empty(m, dtype=torch.int32, device=dev)
+    sizes = torch.empty(m, dtype=torch.int32, device=dev)
+    labels = torch.empty(K, dtype=torch.int32, device=dev)
+    if K == 0:
+        return centres, sizes, labels
+    lib_ = lib or get_lib()
+    nbytes = lib_.call("dlpd_pose_cluster_ws", K)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib_.call("dlpd_interface_cluster", _ptr(rec_bits) if rec_bits.shape[1] else None, _ptr(lig_bits) if lig_bits.shape[1] else None, K,
+              rec_bits.shape[1], lig_bits.shape[1], q, m, _ptr(centres), _ptr(sizes), _ptr(labels), _ptr(count), _ptr(ws), nbytes,
+              _stream(dev))
+    n = int(count.item())
+    return centres[:n], sizes[:n], labels

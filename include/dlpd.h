@@ -665,6 +665,36 @@ int dlpd_pose_contacts_all(const double* poses, int K, const float* rec_atoms, c
                            const int* rec_off_host, const int* lig_off_host, const unsigned* native_bits, float lig_extent,
                            float cutoff, int* n_dec, int* n_corr, void* stream);
 
+/* The interface of every pose as residue bitmaps, and two consumers of them.  BUILD-DEFINED, all five entries: the
+ * reference has no counterpart.  On an error nothing is launched and nothing is written; K = 0 is a no-op everywhere.
+ * dlpd_pose_residue_bits: the arguments, frames, predicate, limits and checks of dlpd_pose_contacts_all without the native bitmap.
+ *   rec_bits (K, Wr) / lig_bits (K, Wl) uint32 on the device, Wr = ceil(NRres / 32), Wl = ceil(NLres / 32): bit (i & 31) of word
+ *   i >> 5 of row k is set iff residue i has an atom at d^2 <= cutoff^2 in float32 of some atom of the partner under pose k.  Every
+ *   word of every row is written; the bits at and above NRres / NLres are zero.
+ * dlpd_interface_profile: over the K rows of the two bitmaps, rec_count / lig_count (int32) = the poses that mark a residue and
+ *   rec_freq / lig_freq (float64) = the sum of weights[k] (K float64 on the device, any values) over those poses.  The order of the
+ *   sum depends on K alone: poses in chunks of 1,024, ascending within a chunk from +0, a set bit adds weights[k] (no product);
+ *   the chunk partials are added in ascending order starting from the first.  ws: the partials,
+ *   dlpd_interface_profile_ws(K, NRres, NLres) bytes (0 for unsupported sizes), 8-byte aligned.  K <= 65536, NRres <= 8192,
+ *   NLres <= 1024 (else DLPD_ERR_UNSUPPORTED); a null pointer, K < 0, no residues, a short workspace: DLPD_ERR_ARG.
+ * dlpd_interface_within: a pose's fingerprint F is its Wr + Wl words (either may be 0, not both; the bitmap of a side with no
+ *   words may be null).  mask has the layout of dlpd_pose_within: bit (j & 63) of mask[i * W + (j >> 6)], W = ceil(K / 64), is set
+ *   iff |F_i & F_j| * 1024 >= q * |F_i | F_j| -- integers only; two empty fingerprints are neighbours, the diagonal is set, the
+ *   bitmap is symmetric; bits of columns >= K are zero.  K <= 65536, Wr <= 256, Wl <= 32 (else DLPD_ERR_UNSUPPORTED); a null
+ *   pointer, a negative size, q outside 0..1024: DLPD_ERR_ARG.
+ * dlpd_interface_cluster: that bitmap, then the greedy scan of dlpd_pose_cluster on it, with that entry's outputs, max_clusters
+ *   and workspace: dlpd_pose_cluster_ws(K) bytes; the bitmap never leaves the device. */
+int dlpd_pose_residue_bits(const double* poses, int K, const float* rec_atoms, const int* rec_off, const float* rec_sph, int NRa,
+                           int NRres, const float* lig_atoms, const int* lig_off, const float* lig_sph, int NLa, int NLres,
+                           const int* rec_off_host, const int* lig_off_host, float lig_extent, float cutoff, unsigned* rec_bits,
+                           unsigned* lig_bits, void* stream);
+size_t dlpd_interface_profile_ws(int K, int NRres, int NLres);
+int dlpd_interface_profile(const unsigned* rec_bits, const unsigned* lig_bits, int K, int NRres, int NLres, const double* weights,
+                           double* rec_freq, double* lig_freq, int* rec_count, int* lig_count, void* ws, size_t ws_bytes, void* stream);
+int dlpd_interface_within(const unsigned* rec_bits, const unsigned* lig_bits, int K, int Wr, int Wl, int q, void* mask, void* stream);
+int dlpd_interface_cluster(const unsigned* rec_bits, const unsigned* lig_bits, int K, int Wr, int Wl, int q, int max_clusters,
+                           int* centres, int* sizes, int* labels, int* count, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,15 @@ without the benchmark table: representation -> exhaustive rotation x translation
                                            # (default 10) and the first FAR poses (default 10) of the list the run ends with -- the
                                            # clustered one if --cluster was given, else the top list -- each labelled by
                                            # Docker.evaluate(fnonnat=True); the target is named after <out>
+        [--interface [N][:boltzmann:T | :rank]]  # which residues of each protein the top list puts in the interface
+                                           # (Docker.interface: a residue counts for a pose when one of its atoms lies within 5 A
+                                           # of the partner; weights uniform, or Boltzmann in the score at temperature T, or
+                                           # 1 / (1 + position)) -> <out>.interface.txt (side, chain, residue, name, count,
+                                           # frequency per line) and the N (default 10) most frequent residues of each side as
+                                           # CHAIN:RESNUM, the form --restraint takes
+        [--cluster-interface THRESHOLD[:KEEP]]  # cluster the top list by the similarity of the poses' interfaces: two poses are
+                                           # neighbours when the Jaccard index of their residue sets is >= THRESHOLD (0..1)
+                                           # (Docker.cluster_interface) -> <out>.iclustered.dat and <out>.iclustered.sizes.txt
 
 Multi-GPU: launch with torch.distributed.run; rotations are sharded over the ranks, rank 0 writes."""
 import argparse
@@ -110,6 +119,60 @@ def cluster_and_write(docker, prepared, out, radius, keep=None, poses=None, rank
     return name, sizes_name
 
 
+def parse_interface(spec):
+    """[N][:boltzmann:T | :rank] -> (residues printed per side, weights, temperature or None)"""
+    part = str(spec).split(":")
+    n = int(part[0]) if part[0] else 10
+    if len(part) == 1:
+        return n, "uniform", None
+    if part[1] == "rank" and len(part) == 2:
+        return n, "rank", None
+    if part[1] == "boltzmann" and len(part) == 3 and float(part[2]) > 0.0:
+        return n, "boltzmann", float(part[2])
+    raise ValueError("--interface takes [N][:boltzmann:T | :rank] with T > 0, got %r" % (spec,))
+
+
+def parse_cluster_interface(spec):
+    """THRESHOLD[:KEEP] -> (Jaccard threshold in [0, 1], keep or None)"""
+    threshold, keep = parse_cluster(spec)
+    if not 0.0 <= threshold <= 1.0:
+        raise ValueError("--cluster-interface takes a THRESHOLD in [0, 1], got %r" % (spec,))
+    return threshold, keep
+
+
+def interface_and_write(docker, complex, out, n=10, weights="uniform", temperature=None, poses=None, rank=0):
+    """The --interface step: ``Docker.interface`` on ``poses`` (None: the top list), then <out>.interface.txt and the ``n`` most
+    frequent residues of each side, by ``rank`` 0 (every rank treats the same gathered list) -> the file's name"""
+    prof = docker.interface(complex, poses=poses, weights=weights, temperature=temperature)
+    name = (out[:-4] if out.endswith(".dat") else out) + ".interface.txt"
+    if rank == 0:
+        docker.new_log(name, rewrite=True)
+        docker.write_interface()
+        docker.cleanup()
+        print("wrote", name, "(%d poses; %d receptor and %d ligand residues in some interface)" %
+              (prof["K"], int((prof["rec_count"] > 0).sum()), int((prof["lig_count"] > 0).sum())))
+        for side in ("receptor", "ligand"):
+            print("  %-8s" % side, " ".join(docker.interface_residues(side, n=n)))
+    return name
+
+
+def cluster_interface_and_write(docker, complex, out, threshold, keep=None, poses=None, rank=0):
+    """The --cluster-interface step: ``Docker.cluster_interface`` on ``poses`` (None: the top list), then <out>.iclustered.dat
+    and <out>.iclustered.sizes.txt written by ``rank`` 0"""
+    docker.cluster_interface(complex, poses=poses, threshold=threshold, keep=keep)
+    stem = (out[:-4] if out.endswith(".dat") else out) + ".iclustered"
+    name, sizes_name = stem + ".dat", stem + ".sizes.txt"
+    if rank == 0:
+        docker.new_log(name, rewrite=True)
+        docker.write_clustered_conformations()
+        docker.cleanup()
+        sizes = [e[4] for e in docker.clustered_list]
+        with open(sizes_name, "w") as f:
+            f.write("".join("%d\n" % s for s in sizes))
+        print("wrote", name, "(%d interface clusters of %d poses, largest %d)" % (len(sizes), sum(sizes), max(sizes) if sizes else 0))
+    return name, sizes_name
+
+
 def evaluation_summary(ev):
     """The best class and the lowest I-RMSD among the first 1 / 10 / 100 / all poses, and the rank of the first pose of class
     >= 1 (1-based; None: there is none) -> (rows [(n, best class, lowest irmsd)], rank)"""
@@ -184,6 +247,8 @@ def main():
     ap.add_argument("--exclusion", default=0, type=parse_exclusion, metavar="R")
     ap.add_argument("--restraint", default=[], action="append", nargs=3, metavar=("REC_SEL", "LIG_SEL", "DMAX[:DMIN]"))
     ap.add_argument("--restraints-needed", default=None, type=int, metavar="M")
+    ap.add_argument("--interface", default=None, nargs="?", const="", type=parse_interface, metavar="[N][:boltzmann:T|:rank]")
+    ap.add_argument("--cluster-interface", default=None, type=parse_cluster_interface, metavar="THRESHOLD[:KEEP]")
     args = ap.parse_args()
     if args.restraints_needed is not None and not args.restraint:
         ap.error("--restraints-needed needs --restraint")
@@ -268,6 +333,13 @@ def main():
         ddir, near, far = parse_decoys(args.decoys)
         decoys_and_write(docker, native, ddir, args.out, args.receptor, args.ligand,
                          poses=docker.clustered_list if args.cluster is not None else None, near=near, far=far, rank=rank)
+    if args.interface is not None or args.cluster_interface is not None:      # (last: --cluster-interface replaces clustered_list)
+        from deeplocalproteindocking_amd.Results.InterfaceSelection import complex_reference
+        complex_ = complex_reference(args.receptor, args.ligand).to(dev)
+        if args.interface is not None:
+            interface_and_write(docker, complex_, args.out, *args.interface, rank=rank)
+        if args.cluster_interface is not None:
+            cluster_interface_and_write(docker, complex_, args.out, args.cluster_interface[0], args.cluster_interface[1], rank=rank)
     if world > 1:
         dist.destroy_process_group()
 
